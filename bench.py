@@ -1,12 +1,15 @@
 """bench.py — headline benchmark of the FasterSeg hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32] [--train-dtype fp32|bf16] [--workloads c2,c3,c4,c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32] [--dump-outputs DIR]
+    python bench.py --full [--train-dtype fp32|bf16] [--workloads c2,c3,c4,c5] ...
 
 ONE JSON line on rank 0.  Top level = BASELINE.json configs[1] (C2): searched student (arch_1) inference at 1x3x1024x2048,
-frames/s, input resident in HBM, the whole forward replayed from one hipGraph (fasterseg_amd.engine).  Before anything is
-timed the engine's logits are checked against the CPU oracle on the same weights and input (bf16: relative error <= 5e-2
-and arg-max agreement >= 97 %; fp32: <= 1e-3) — a frame rate of a wrong answer is never printed.
+frames/s, input resident in HBM, the whole forward replayed from one hipGraph (fasterseg_amd.engine).  A plain run does only
+that: it builds the engine, warms up, times exactly K steps (`ms_per_step` = one step), writes the last step's logits (a fixed
+seeded sample of pixels) with --dump-outputs and prints the line.  Everything else runs with --full:
 
+With --full, before anything is timed the engine's logits are checked against the CPU oracle on the same weights and input (bf16:
+relative error <= 5e-2 and arg-max agreement >= 97 %; fp32: <= 1e-3) — a frame rate of a wrong answer is never printed — and
 `workloads` carries every BASELINE configuration with its own ms_per_step, images/s, `roofline` and `cpu_baseline`:
   C2_student_infer      the top-level numbers again
   C3_supernet_pretrain  `_loss(pretrain=True)`: max / min / random / random width passes, backward, clip, SGD; 3 x 3x256x512
@@ -16,7 +19,7 @@ and arg-max agreement >= 97 %; fp32: <= 1e-3) — a frame rate of a wrong answer
 The train steps are restated in fasterseg_amd/train_step.py from search/train_search.py:215-251 and train/train.py:219-271.
 With N > 1 (one rank per GPU, RCCL) inference runs as independent replicas (it does not shard: no data-path collective,
 "weak") and the three train steps run data-parallel with the flat-gradient all-reduce, so every --gpus N run exercises the
-collective path; launched without torchrun, `--gpus N` re-executes itself under torch.distributed.run.
+collective path; launched without torchrun, `--gpus N` starts itself under torch.distributed.run as a child process.
 
 Every train workload is gated like C2: the loss of the FIRST step of the stepper that is about to be timed is compared with the CPU
 oracle on the same weights / batch / RNG seeds (`parity` inside each workload; a miss aborts).  A train workload's `value` / `dtype` are
@@ -27,8 +30,8 @@ stream (hipExtLaunchKernelGGL; fasterseg_amd/census.py, csrc/census.hip): achiev
 kernel family / the sum of their measured durations - the figures tools/roofline_from_profile.py recomputes from the rocprofv3
 tables under profiles/.  cpu_baseline: the CPU oracle (oracle/, fixture-pinned port of the
 reference modules on torch-CPU kernels) on a bounded sample of the same workload, on this host's cores.
-A step count whose timed region would be shorter than --min-seconds is raised (reported as `steps`; `steps_requested` keeps
-the flag).
+Without an explicit --steps, a step count whose timed region would be shorter than --min-seconds is raised (reported as `steps`;
+`steps_requested` keeps the flag); an explicit --steps K is timed as exactly K steps.
 """
 import argparse
 import json
@@ -63,7 +66,14 @@ def parse():
     ap.add_argument("--train-dtype", default="fp32", choices=["bf16", "fp32"],
                     help="precision of each train workload's `value` (C3/C4/C5): fp32 = the reference's arithmetic (default); the other "
                          "precision is timed as a labelled extra")
-    ap.add_argument("--workloads", default="c2,c3,c4,c5", help="comma list of c2,c3,c4,c5 (c2 is always the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the CPU-oracle parity gates, the train workloads (C3/C4/C5), roofline censuses, "
+                         "the other-precision legs, the class-map engine, CPU baselines, device clocks.  Without it a run builds the C2 "
+                         "engine, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last C2 step computed to DIR/*.npy (float32; a fixed seeded sample of "
+                         "the logits' pixels, all classes)")
+    ap.add_argument("--workloads", default=None, help="comma list of c2,c3,c4,c5 (c2 is always the headline; default c2, with --full all four)")
     ap.add_argument("--train-steps", type=int, default=None, help="timed steps of every train workload (default 10; with an explicit --steps K: K bounded to 10..50)")
     ap.add_argument("--train-warmup", type=int, default=3)
     ap.add_argument("--min-seconds", type=float, default=0.5, help="minimum length of every timed region")
@@ -74,10 +84,15 @@ def parse():
     ap.add_argument("--no-class-map", action="store_true", help="skip the class-map (evaluator) variant of the C2 engine")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="CPU budget of each cpu_baseline sample")
     ap.add_argument("--dump-plan", default=None, help="write the per-launch table of the C2 plan (json) here")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
-                    help="everything that is not in the (small) JSON line goes here: autotune logs, per-kernel tables, clocks, method strings")
-    ap.add_argument("--regions", type=int, default=5, help="with an explicit --steps: timed regions of EXACTLY that many steps; the median is reported")
+    ap.add_argument("--detail", default=None,
+                    help="everything that is not in the (small) JSON line goes here: autotune logs, per-kernel tables, clocks, method strings "
+                         "(default with --full: bench_detail.json; otherwise only written when given)")
+    ap.add_argument("--regions", type=int, default=1, help="with an explicit --steps: timed regions of EXACTLY that many steps; the median is reported")
     args = ap.parse_args()
+    if args.workloads is None:
+        args.workloads = "c2,c3,c4,c5" if args.full else "c2"
+    if args.detail is None and args.full:
+        args.detail = os.path.join(ROOT, "bench_detail.json")
     args.steps_requested = args.steps
     args.exact = args.steps is not None                # an explicit --steps K is timed as exactly K steps (never raised)
     if args.steps is None:
@@ -87,6 +102,8 @@ def parse():
     if args.train_steps is None:                       # the train workloads follow --steps too, bounded so a huge K stays minutes
         args.train_steps = max(10, min(args.steps, 50)) if args.exact else 10
     args.workloads = [w.strip().lower() for w in args.workloads.split(",") if w.strip()]
+    if not args.full and any(w != "c2" for w in args.workloads):
+        raise SystemExit("bench.py: the train workloads (c3, c4, c5) run with --full")
     return args
 
 
@@ -102,7 +119,11 @@ def dist_setup(args):
         s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr",
                "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execvp(cmd[0], cmd)
+        # a child process, not exec: this process has already initialised the GPU (device_count above), and replacing a process
+        # that holds the device open is not safe
+        import subprocess
+        rc = subprocess.run(cmd).returncode
+        raise SystemExit(rc if rc >= 0 else 128 - rc)
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
@@ -252,36 +273,61 @@ def roofline_from_profile(rows, dtype):
     return out, families, total_ms
 
 
+DUMP_SEED = 20240601
+DUMP_PIXEL_FRACTION = 4                              # one pixel in four: 19 classes x 524288 pixels x 4 B = 40 MB of the 159 MB logits
+
+
+def dump_outputs(directory, logits):
+    """What the timed C2 step hands its caller - the fp32 logits (N, C, H, W) - as DIR/logits_sample.npy: every class at a fixed,
+    seeded set of pixels (ascending flat index; the same set on every run), shape (N, C, pixels), float32.  Called after the timed
+    region, which ends with a device synchronize."""
+    import numpy as np
+    n, c, h, w = logits.shape
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    idx = torch.randperm(h * w, generator=g)[:h * w // DUMP_PIXEL_FRACTION].sort().values
+    sample = logits.reshape(n, c, h * w).index_select(2, idx.to(logits.device)).float().cpu().numpy()
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "logits_sample.npy"), sample)
+
+
 def run_student_infer(args, world, rank, backend):
     from fasterseg_amd import archs, engine
     from oracle import ref_ops
     from oracle.seeded import resolve_aliases
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     shape = (1, 3, 1024, 2048)
-    with open(os.path.join(ROOT, "tests", "golden", "arch_1.json")) as f:
-        meta = json.load(f)["eval_21"]                    # decoded structure of arch_1 (test fixture): only the oracle reads it
     net = archs.build_derived(1, training=False)          # eval build, branches chosen by objective_acc_lat -> [2, 1]
     archs.init_weight(net, seed=12345)
-    params = resolve_aliases({k: v.detach().clone() for k, v in net.state_dict().items()}, meta)
+    if args.full:
+        with open(os.path.join(ROOT, "tests", "golden", "arch_1.json")) as f:
+            meta = json.load(f)["eval_21"]                # decoded structure of arch_1 (test fixture): only the oracle reads it
+        params = resolve_aliases({k: v.detach().clone() for k, v in net.state_dict().items()}, meta)
     net = net.cuda().eval()
     eng = engine.InferenceEngine(net, shape, dtype=dtype, logits_dtype=torch.float32)
     x = torch.randn(shape, generator=torch.Generator().manual_seed(rank))
-    # ---- parity gate: the engine that is about to be timed vs the CPU oracle, same weights, same frame
-    cores = torch.get_num_threads()
-    with torch.no_grad():
-        t0 = time.perf_counter()
-        want = ref_ops.derived_forward(params, meta, x)
-        oracle_s = time.perf_counter() - t0
-        got = eng(x.cuda()).float().cpu()
-    err = float((got - want).abs().max())
-    rel = err / float(want.abs().max())
-    agree = float((got.argmax(1) == want.argmax(1)).float().mean())
-    ok = (err <= 1e-3) if args.dtype == "fp32" else (rel <= 5e-2 and agree >= 0.97)
-    parity = {"vs": "oracle.ref_ops.derived_forward (CPU fp32), same weights and frame", "max_abs_err": err, "rel_to_max_logit": rel,
-              "argmax_agreement": agree, "bar": "fp32: max_abs_err <= 1e-3; bf16: rel <= 5e-2 and argmax >= 0.97", "pass": bool(ok)}
-    if not ok:
-        raise SystemExit("bench.py: engine logits do not match the CPU oracle: %s" % json.dumps(parity))
+    parity = None
+    if args.full:
+        # ---- parity gate: the engine that is about to be timed vs the CPU oracle, same weights, same frame
+        cores = torch.get_num_threads()
+        with torch.no_grad():
+            t0 = time.perf_counter()
+            want = ref_ops.derived_forward(params, meta, x)
+            oracle_s = time.perf_counter() - t0
+            got = eng(x.cuda()).float().cpu()
+        err = float((got - want).abs().max())
+        rel = err / float(want.abs().max())
+        agree = float((got.argmax(1) == want.argmax(1)).float().mean())
+        ok = (err <= 1e-3) if args.dtype == "fp32" else (rel <= 5e-2 and agree >= 0.97)
+        parity = {"vs": "oracle.ref_ops.derived_forward (CPU fp32), same weights and frame", "max_abs_err": err, "rel_to_max_logit": rel,
+                  "argmax_agreement": agree, "bar": "fp32: max_abs_err <= 1e-3; bf16: rel <= 5e-2 and argmax >= 0.97", "pass": bool(ok)}
+        if not ok:
+            raise SystemExit("bench.py: engine logits do not match the CPU oracle: %s" % json.dumps(parity))
+    else:
+        with torch.no_grad():
+            eng(x.cuda())                                 # the frame every timed step replays
     elapsed, steps = timed_region(eng.run, args.steps, args.warmup, world, args.min_seconds, args.exact, args.regions)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng.output)
     fps = world * steps / elapsed
     line = {
         "value": round(fps, 2), "unit": "frames/s", "steps": steps, "warmup": args.warmup, "ms_per_step": round(elapsed / steps * 1e3, 4),
@@ -303,7 +349,7 @@ def run_student_infer(args, world, rank, backend):
         "vs_baseline_note": "per-GPU fps / 163.9 FPS published on GTX 1080Ti + TensorRT fp32 (nearest-resample latency/ variant of "
                             "the network); this run is the bilinear train/ network",
     }
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # in-frame: every launch of the plan timed by its own HIP event pair while whole frames are issued in plan order (what
         # rocprofv3's kernel trace of a frame shows); isolated: each launch replayed 20x alone, cache-warm (the round-1/2 figure)
         rows = eng.profile_in_frame()
@@ -324,7 +370,7 @@ def run_student_infer(args, world, rank, backend):
         if args.dump_plan:
             with open(args.dump_plan, "w") as f:
                 json.dump(rows, f, indent=1)
-    if rank == 0 and args.dtype == "bf16" and not args.no_fp32_leg:
+    if rank == 0 and args.full and args.dtype == "bf16" and not args.no_fp32_leg:
         # north_star's bar in ONE record: ">= 163 fps with logits within 1e-3 of the reference" is an fp32 statement (the published
         # 163.9 FPS is TensorRT fp32, latency/run_latency.py:81) - the same engine in fp32 storage + exact-fp32 MFMA, gated and timed
         torch.cuda.empty_cache()
@@ -341,7 +387,7 @@ def run_student_infer(args, world, rank, backend):
                         "note": PRECISION["fp32"] + "; logits vs oracle.ref_ops.derived_forward on the same weights and frame, bar 1e-3"}
         del eng32, got32
         torch.cuda.empty_cache()
-    if rank == 0 and not args.no_class_map:
+    if rank == 0 and args.full and not args.no_class_map:
         # the evaluator path: same network, class map (uint8) instead of fp32 logits as the output
         eng_c = engine.InferenceEngine(net, shape, dtype=dtype, output="classes")
         cls = eng_c(x.cuda())
@@ -352,7 +398,7 @@ def run_student_infer(args, world, rank, backend):
                              "note": "validation frames: the x8 up-sample and the evaluator's arg-max (tools/engine/evaluator.py:223) in one "
                                      "launch, 2 MB uint8 out instead of 159 MB fp32 logits"}
         del eng_c
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline:
         def cpu_frame():
             with torch.no_grad():
                 ref_ops.derived_forward(params, meta, x)
@@ -725,7 +771,8 @@ def build_line(c2, train, world, steps_requested, dtype, detail_path):
             "config": {"workload": _short(c2["config"]["workload"], 220), "parallelism": _short(c2["config"]["parallelism"], 100)}}
     if steps_requested is not None and steps_requested != c2["steps"]:
         line["steps_requested"] = steps_requested
-    line["parity"] = compact_workload(c2)["parity"]
+    if c2.get("parity"):
+        line["parity"] = compact_workload(c2)["parity"]
     for k in ("alg_gflop_per_frame", "alg_mb_per_frame"):
         if k in c2:
             line[k] = c2[k]
@@ -829,10 +876,10 @@ def main():
     c2 = None
 
     def clocked(name, fn):
-        if rank == 0:
+        if rank == 0 and args.full:
             clocks[name] = {"before": device_clocks()}
         out = fn()
-        if rank == 0:
+        if rank == 0 and args.full:
             clocks[name]["after"] = device_clocks()
         return out
     for key in order:
@@ -847,15 +894,17 @@ def main():
         c2 = clocked("C2_student_infer", lambda: run_student_infer(args, world, rank, backend))
     if rank == 0:
         line, detail = build_line(c2, train, world, args.steps_requested, args.dtype, args.detail)
-        detail["clocks"] = clocks
         detail["argv"] = sys.argv[1:]
         detail["order"] = order
-        detail["host"] = host_info()          # the supernet steps are host-bound: the box's CPU is part of the result
-        try:
-            with open(args.detail, "w") as f:
-                json.dump(detail, f, indent=1, default=str)
-        except OSError as e:
-            line["detail"] = "not written: %r" % (e,)
+        if args.full:
+            detail["clocks"] = clocks
+            detail["host"] = host_info()      # the supernet steps are host-bound: the box's CPU is part of the result
+        if args.detail:
+            try:
+                with open(args.detail, "w") as f:
+                    json.dump(detail, f, indent=1, default=str)
+            except OSError as e:
+                line["detail"] = "not written: %r" % (e,)
         text = json.dumps(fit_line(line))
         sys.stdout.flush()
         print(text, flush=True)

@@ -3,6 +3,8 @@ recorded `parsed: null`).  Built here from a canned full result - round 3's own 
 import json
 import os
 
+import pytest
+
 import bench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -132,3 +134,61 @@ def test_cpu_baseline_sweeps_the_thread_count():
     assert out["cores"] == min(2, before)                      # the fastest candidate
     assert "threads swept" in out["sample"]
     assert set(seen) <= {1, min(2, before)}
+
+
+def _parse(monkeypatch, *argv):
+    import sys
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+    return bench.parse()
+
+
+def test_a_plain_run_times_only_the_headline(monkeypatch):
+    """Without --full the run is C2 alone: no train workloads, no detail file unless named, one region of exactly --steps steps."""
+    a = _parse(monkeypatch, "--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert not a.full and a.workloads == ["c2"] and a.detail is None and a.dump_outputs is None
+    assert a.steps == 7 and a.exact and a.regions == 1 and a.warmup == 2
+    full = _parse(monkeypatch, "--full", "--steps", "7")
+    assert full.workloads == ["c2", "c3", "c4", "c5"] and full.detail.endswith("bench_detail.json")
+    assert _parse(monkeypatch, "--full", "--workloads", "c4").workloads == ["c4"]
+    with pytest.raises(SystemExit):
+        _parse(monkeypatch, "--workloads", "c3")                 # the train workloads belong to --full
+
+
+def test_dump_outputs_is_a_fixed_float32_sample_under_64_mb(tmp_path):
+    import numpy as np
+    import torch
+    logits = torch.arange(2 * 3 * 8 * 16, dtype=torch.float32).reshape(2, 3, 8, 16)
+    bench.dump_outputs(str(tmp_path / "a"), logits)
+    bench.dump_outputs(str(tmp_path / "b"), logits)
+    a, b = np.load(tmp_path / "a" / "logits_sample.npy"), np.load(tmp_path / "b" / "logits_sample.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 3, 8 * 16 // bench.DUMP_PIXEL_FRACTION)
+    assert np.array_equal(a, b)                                  # the same pixels on every run
+    flat = logits.reshape(2, 3, -1).numpy()
+    idx = (a[0, 0]).astype(np.int64)                             # logits[0, 0] holds the flat pixel index itself
+    assert np.all(np.diff(idx) > 0) and np.array_equal(a, flat[:, :, idx])
+    # the benchmarked frame: 19 classes at 1024 x 2048
+    assert 19 * (1024 * 2048 // bench.DUMP_PIXEL_FRACTION) * 4 <= 64 * 2 ** 20
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_the_requested_steps_and_dumps_its_output(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` as a fresh process: one line with the headline keys, exactly K
+    timed steps, and the last step's logits sample in DIR."""
+    import subprocess
+    import sys
+    import numpy as np
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "3", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 30 and d["warmup"] == 3 and d["unit"] == "frames/s" and d["dtype"] == "bf16"
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 0.01 * d["value"]
+    assert "workloads" in d and set(d["workloads"]) == {"C2_student_infer"} and "roofline" not in d
+    sample = np.load(out / "logits_sample.npy")
+    assert sample.dtype == np.float32 and sample.shape == (1, 19, 1024 * 2048 // bench.DUMP_PIXEL_FRACTION)
+    assert np.isfinite(sample).all() and float(np.abs(sample).max()) > 0

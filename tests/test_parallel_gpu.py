@@ -151,7 +151,7 @@ def test_bench_two_ranks_over_gloo_runs_the_supernet_step(tmp_path):
     env = dict(os.environ, FS_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workloads", "c3", "--steps", "50", "--warmup", "5", "--train-steps", "2",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--workloads", "c3", "--steps", "50", "--warmup", "5", "--train-steps", "2",
            "--train-warmup", "1", "--min-seconds", "0.05", "--no-cpu-baseline", "--no-class-map", "--no-fp32-leg", "--detail", str(tmp_path / "detail.json")]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -180,7 +180,7 @@ def test_bench_two_ranks_over_gloo_runs_the_collective_path(tmp_path):
     env = dict(os.environ, FS_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workloads", "c4", "--steps", "50", "--warmup", "5", "--train-steps", "2",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--workloads", "c4", "--steps", "50", "--warmup", "5", "--train-steps", "2",
            "--train-warmup", "1", "--min-seconds", "0.05", "--no-cpu-baseline", "--no-class-map", "--no-fp32-leg", "--detail", str(tmp_path / "detail.json")]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

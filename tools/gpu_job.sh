@@ -26,7 +26,7 @@ case $job in
   final)      # the round's evidence on ONE box: whole GPU suite, the default bench line, rocprofv3 kernel tables of the timed steps
     tag=${1:-r05}
     timeout 1500 python -W ignore -m pytest tests -m gpu -q --timeout 900 --durations=10 > $O/${tag}_gpu_tests.log 2>&1; echo "pytest rc=$?"; tail -4 $O/${tag}_gpu_tests.log | cut -c1-200
-    timeout 900 python -W ignore bench.py --steps 20 --warmup 5 --detail $O/${tag}_bench_default_detail.json > $O/${tag}_bench_default.json 2> $O/${tag}_bench_default.err; echo "bench rc=$?"
+    timeout 900 python -W ignore bench.py --full --steps 20 --warmup 5 --detail $O/${tag}_bench_default_detail.json > $O/${tag}_bench_default.json 2> $O/${tag}_bench_default.err; echo "bench rc=$?"
     tail -c 3200 $O/${tag}_bench_default.json; tail -2 $O/${tag}_bench_default.err
     bash tools/prof_round.sh steps $tag 2>&1 | tail -6
     ;;

@@ -14,7 +14,7 @@ export FS_ENGINE_PLAN=$O/${TAG}_c2_plan_choices.json
 if [ $what = all ] || [ $what = c2 ]; then
   rm -f $FS_ENGINE_PLAN.*
   # tune the plan once on the idle device (the bench's own C2 line), then replay exactly that plan under the profiler
-  timeout 400 python bench.py --workloads c2 --no-cpu-baseline --no-class-map --dump-plan $O/${TAG}_c2_plan_inframe_bf16.json > $O/${TAG}_bench_c2_planned.json 2>/dev/null
+  timeout 400 python bench.py --full --workloads c2 --no-cpu-baseline --no-class-map --dump-plan $O/${TAG}_c2_plan_inframe_bf16.json > $O/${TAG}_bench_c2_planned.json 2>/dev/null
   python tools/extract_c2.py $O/${TAG}_bench_c2_planned.json 2>/dev/null | head -3
   cd /tmp; rm -rf /tmp/prof_c2
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c2 -o run -- python $R/tools/profile_frame.py 60 $O/${TAG}_c2_plan_bf16.json > $O/${TAG}_prof_c2.log 2>&1
