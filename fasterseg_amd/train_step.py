@@ -247,10 +247,15 @@ class SupernetStep:
         out = self.model.forward_multi(imgs, list(group), batch_tails=True)
         from .model_search import JointLogits
         if isinstance(out, JointLogits):
-            # the passes' logits along the batch: the criterion is a mean over the valid pixels, every pass sees the same labels, so
-            # sum_p CE(logit_p, target) = passes * CE(logits of all passes, target repeated)
-            t = torch.cat([target] * out.passes)
-            return out.passes * sum(self.model._criterion(logit, t) for logit in out.logits)
+            # the passes' logits along the batch.  For plain mean-over-valid-pixels CE every pass sees the same labels, hence the same
+            # number of valid pixels, so sum_p CE(logit_p, target) = passes * CE(logits of all passes, target repeated).  A criterion that
+            # selects or weights pixels per call (OHEM's threshold and min_kept, class weights, another reduction) does not pool like
+            # that: it gets each pass's chunk of the batch on its own.
+            crit = self.model._criterion
+            if type(crit) is torch.nn.CrossEntropyLoss and crit.reduction == "mean" and crit.weight is None:
+                t = torch.cat([target] * out.passes)
+                return out.passes * sum(crit(logit, t) for logit in out.logits)
+            out = out.split()
         total = 0
         for logits in out:
             total = total + sum(self.model._criterion(logit, target) for logit in logits)

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import ref_loader
-from .seeded import seeded_input, seeded_state
+from .seeded import search_iteration_batch, seeded_input, seeded_state
 
 GOLD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 WML = [4. / 12, 6. / 12, 8. / 12, 10. / 12, 1.]
@@ -490,7 +490,56 @@ def l16_sampled(key):
     return (not key.startswith("cells.")) or zlib.crc32(key.encode()) % 16 == 0
 
 
-def gen_supernet_l16():
+def _savez_fixed(path, store):
+    """np.savez_compressed with the archive's timestamps and member order fixed, so that a re-run reproduces the file bit for bit."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as zf:
+        for key in sorted(store):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(store[key]), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            zf.writestr(info, buf.getvalue())
+
+
+# 7d. the same `_loss` forward + backward at the BENCHMARKED batches (search/config_search.py:88-101: pretrain 3 x 3x256x512, search
+#     2 x 3x224x448), distinct samples: the grouped BatchNorm of a joint tail normalises each pass's half of the batch, BN statistics
+#     reduce over N x H x W, the grouped launches stride over the batch - none of which a batch-1 fixture can tell apart.  Also the
+#     running statistics after the step of the BatchNorms outside the cells (stem, refinement, heads) and of a few deep-cell ones
+#     that more than one pass reached: a momentum update applied twice, in another order or over the wrong half of the batch shows there.
+L16_BATCH_CASES = (("pretrain", (3, 3, 256, 512)), ("search", (2, 3, 224, 448)))
+SMALL = 2000                 # the newer fixtures keep at most ~SMALL elements of a stored tensor (file size)
+
+
+def _put_small(store, key, t):
+    """fp32 copy of `t`; above SMALL elements flat[::stride] under key+'@stride', stride = ceil(size / SMALL)."""
+    a = _np(t).astype(np.float32)
+    stride = -(-a.size // SMALL)
+    if stride > 1:
+        store["%s@%d" % (key, stride)] = a.reshape(-1)[::stride].copy()
+    else:
+        store[key] = a
+
+
+def _l16_bn_after(net, store, prefix):
+    """Running mean / var after the step of every BatchNorm outside the cells and of up to 8 deep-cell ones (layer >= 8) that more
+    than one pass updated; returns {module: num_batches_tracked}."""
+    import zlib
+    bufs = dict(net.named_buffers())
+    seen = {k[:-len(".num_batches_tracked")]: int(v) for k, v in bufs.items() if k.endswith(".num_batches_tracked") and int(v) > 0}
+    outside = sorted(m for m in seen if not m.startswith("cells."))
+    deep = sorted((m for m in seen if m.startswith("cells.") and int(m.split(".")[1]) >= 8 and seen[m] >= 2),
+                  key=lambda m: zlib.crc32(m.encode()))[:8]
+    chosen = {}
+    for m in outside + sorted(deep):
+        store["%s/bn/%s.running_mean" % (prefix, m)] = _np(bufs[m + ".running_mean"]).copy()      # (not a view: the next case reloads the buffers)
+        store["%s/bn/%s.running_var" % (prefix, m)] = _np(bufs[m + ".running_var"]).copy()
+        chosen[m] = seen[m]
+    return chosen
+
+
+def _gen_supernet_l16(cases, name, bn_stats=False):
     import hashlib
     store, meta = {}, {}
     with ref_loader.reference("search"):
@@ -507,7 +556,7 @@ def gen_supernet_l16():
             net.load_state_dict(sd)
             net = net.to(torch.float64).train()
             meta["num_params"] = int(sum(p.numel() for p in net.parameters()))
-            for mode, shape in L16_CASES:
+            for mode, shape in cases:
                 x = seeded_input(shape, 41).to(torch.float64)
                 g = torch.Generator().manual_seed(42)
                 target = torch.randint(0, 19, (shape[0], shape[2] // 8, shape[3] // 8), generator=g)
@@ -532,13 +581,124 @@ def gen_supernet_l16():
                               "gradnorms": {k: float(named[k].grad.norm()) for k in with_grad if l16_sampled(k)}}
                 for k in L16_GRADS:
                     if named[k].grad is not None:
-                        _put(store, "%s/g/%s" % (mode, k), named[k].grad.float())
+                        (_put_small if bn_stats else _put)(store, "%s/g/%s" % (mode, k), named[k].grad.float())
+                if bn_stats:
+                    meta[mode]["bn_num_batches_tracked"] = _l16_bn_after(net, store, mode)
                 print("supernet L16", mode, shape, float(loss.detach()), "params with grad:", len(with_grad), "norms kept:", len(meta[mode]["gradnorms"]))
         finally:
             torch.Tensor.cuda = real_cuda
-    np.savez_compressed(os.path.join(GOLD, "supernet_l16.npz"), **store)
-    with open(os.path.join(GOLD, "supernet_l16_meta.json"), "w") as f:
-        json.dump(meta, f)
+    if bn_stats:
+        _savez_fixed(os.path.join(GOLD, name + ".npz"), store)
+    else:
+        np.savez_compressed(os.path.join(GOLD, name + ".npz"), **store)
+    with open(os.path.join(GOLD, name + "_meta.json"), "w") as f:
+        json.dump(meta, f, sort_keys=bn_stats)
+
+
+def gen_supernet_l16():
+    _gen_supernet_l16(L16_CASES, "supernet_l16")
+
+
+def gen_supernet_l16_batch():
+    _gen_supernet_l16(L16_BATCH_CASES, "supernet_l16_b", bn_stats=True)
+
+
+# 7e. two full iterations of the search loop (search/train_search.py:225-250) at the C5 batch, 2 x 3x224x448: Architect.step on the
+#     search batch (arch 0, arch 1 with Gumbel widths, max, min + the latency penalty of arch 1 mixed 1:497:2 -> Adam(3e-4, betas
+#     0.5 / 0.999) on alpha / beta / ratio), then the weight step (zero_grad -> `_loss(imgs, target, False)` -> backward ->
+#     clip_grad_norm_(model.parameters(), 5) -> SGD(2e-2, 0.9, 5e-4)).  Per iteration: every architecture gradient the arch step
+#     leaves (and which stay None), the arch `_loss`, the latency, the architecture parameters after Adam, the weight-step loss, the
+#     clip norm over all parameters (the arch step's gradients are still in .grad, and the weight step's backward adds to them) and
+#     over the weights alone, and the SGD update of a few weights.  The reference's own fp32 run of the same iterations is the yardstick.
+SEARCH_ITER_SHAPE = (2, 3, 224, 448)
+SEARCH_ITER_KEYS = ("stem.0.0.conv.0.weight", "stem.1.1.conv1.weight", "cells.1.0._op._ops.3.conv1.weight", "cells.7.1._op._ops.1.conv1.weight",
+                    "cells.9.1.downsample._ops.0.conv2.weight", "cells.15.2._op._ops.2.conv1.weight", "refine32.1.1.conv.0.weight",
+                    "head0.1.conv_1x1.weight", "head12.1.conv_1x1.bias", "head02.0.conv_1x1.bias")
+
+
+def gen_search_iteration_l16(iters=2):
+    store, meta = {}, {}
+    with ref_loader.reference("search"):
+        import model_search
+        import architect as architect_mod
+        real_cuda, real_module_cuda = torch.Tensor.cuda, torch.nn.Module.cuda
+        torch.Tensor.cuda = lambda self, *a, **k: self
+        torch.nn.Module.cuda = lambda self, *a, **k: self        # nn.KLDivLoss().cuda() (architect.py:21)
+        try:
+            crit = torch.nn.CrossEntropyLoss(ignore_index=255)
+            args = type("Args", (), dict(momentum=0.9, weight_decay=5e-4, arch_learning_rate=3e-4, latency_weight=[0, 1e-2]))
+            runs = {}
+            for tag, dt in (("f64", torch.float64), ("f32", torch.float32)):
+                net = model_search.Network_Multi_Path(criterion=crit, **L16_CFG)
+                sd = seeded_state(net.state_dict(), 778)
+                for k in list(sd):
+                    if k.split("_")[0] in ("alpha", "beta", "ratio"):
+                        sd[k] = sd[k] * 5.0
+                net.load_state_dict(sd)
+                net = net.to(dt).train()
+                architect = architect_mod.Architect(net, args)
+                parameters = []
+                for part in (net.stem, net.cells, net.refine32, net.refine16, net.head0, net.head1, net.head2, net.head02, net.head12):
+                    parameters += list(part.parameters())                                  # train_search.py:84-94
+                optimizer = torch.optim.SGD(parameters, lr=2e-2, momentum=0.9, weight_decay=5e-4)
+                wid = {id(p) for p in parameters}
+                names = dict(net.named_parameters())
+                arch_names = [k for k in names if id(names[k]) not in wid]
+                assert all(k in names for k in SEARCH_ITER_KEYS), [k for k in SEARCH_ITER_KEYS if k not in names]
+                recorded = []
+                plain_loss = net._loss
+                net._loss = lambda *a, **k: recorded.append(plain_loss(*a, **k)) or recorded[-1]     # the arch `_loss` before the penalty
+                net.arch_idx = 0
+                runs[tag] = []
+                for it in range(iters):
+                    imgs, target, imgs_s, target_s = [t.to(dt) if t.is_floating_point() else t for t in search_iteration_batch(it, SEARCH_ITER_SHAPE)]
+                    np.random.seed(300 + it)
+                    torch.manual_seed(400 + it)
+                    del recorded[:]
+                    loss_arch = architect.step(imgs, target, imgs_s, target_s)                  # train_search.py:241
+                    arch_loss = float(recorded[0].detach())
+                    latency = float(architect.latency_supernet)
+                    grads = {k: None if names[k].grad is None else names[k].grad.detach().double().clone() for k in arch_names}
+                    after_adam = {k: names[k].detach().double().clone() for k in arch_names}
+                    optimizer.zero_grad()                                                      # train_search.py:245-250
+                    loss = net._loss(imgs, target, False)
+                    loss.backward()
+                    w_norm = torch.sqrt(sum((p.grad.double() ** 2).sum() for p in parameters if p.grad is not None))
+                    total = torch.nn.utils.clip_grad_norm_(net.parameters(), 5)
+                    optimizer.step()
+                    optimizer.zero_grad()
+                    weights = {k: names[k].detach().double().clone() for k in SEARCH_ITER_KEYS}
+                    runs[tag].append(dict(grads=grads, after_adam=after_adam, weights=weights))
+                    p = "%s/it%d/" % (tag, it)
+                    store[p + "loss_arch"] = np.array([float(loss_arch.detach())])
+                    store[p + "arch_loss"] = np.array([arch_loss])
+                    store[p + "latency"] = np.array([latency])
+                    store[p + "loss"] = np.array([float(loss.detach())])
+                    store[p + "norm_all"] = np.array([float(total)])
+                    store[p + "norm_weights"] = np.array([float(w_norm)])
+                    for k in arch_names:
+                        if grads[k] is not None:
+                            store[p + "arch_grad/" + k] = _np(grads[k])
+                        if tag == "f64":
+                            store[p + "arch_param/" + k] = _np(after_adam[k])
+                    if tag == "f64":
+                        meta["it%d" % it] = {"arch_grad_none": sorted(k for k in arch_names if grads[k] is None)}
+                        for k in SEARCH_ITER_KEYS:
+                            _put_small(store, p + "update/" + k, weights[k] - sd[k].double())      # w after SGD - w0
+                    print("search iteration", tag, it, "arch loss", arch_loss, "latency", latency, "loss", float(loss.detach()),
+                          "clip norm all / weights", float(total), float(w_norm))
+                meta["arch_params"] = arch_names
+            for it in range(iters):          # the yardstick: the reference's fp32 run against its fp64 run
+                r64, r32 = runs["f64"][it], runs["f32"][it]
+                for k in SEARCH_ITER_KEYS:
+                    init = sd[k].double()
+                    du64, du32 = r64["weights"][k] - init, r32["weights"][k] - init
+                    store["f32/it%d/update_err/%s" % (it, k)] = np.array([float((du32 - du64).norm() / (du64.norm() + 1e-30))])
+        finally:
+            torch.Tensor.cuda, torch.nn.Module.cuda = real_cuda, real_module_cuda
+    _savez_fixed(os.path.join(GOLD, "search_iter_l16.npz"), store)
+    with open(os.path.join(GOLD, "search_iter_l16_meta.json"), "w") as f:
+        json.dump(meta, f, sort_keys=True, indent=0)
 
 
 # 8. evaluation metrics (tools/seg_opr/metric.py is pure numpy and imports unmodified)
@@ -635,9 +795,11 @@ def gen_optimizer_trajectory(steps=3):
 def main():
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(max(1, os.cpu_count() or 1))
-    which = sys.argv[1:] or ["arch", "decode", "ops", "nets", "student_step", "lut", "loss", "supernet", "supernet_l16", "eval", "trajectory"]
+    which = sys.argv[1:] or ["arch", "decode", "ops", "nets", "student_step", "lut", "loss", "supernet", "supernet_l16", "supernet_l16_batch",
+                              "search_iter_l16", "eval", "trajectory"]
     for w in which:
-        {"arch": gen_arch, "decode": gen_decode_cases, "ops": gen_ops, "nets": gen_nets, "lut": gen_lut, "loss": gen_loss, "supernet": gen_supernet, "supernet_l16": gen_supernet_l16, "eval": gen_eval, "student_step": gen_student_step, "trajectory": gen_optimizer_trajectory}[w]()
+        {"arch": gen_arch, "decode": gen_decode_cases, "ops": gen_ops, "nets": gen_nets, "lut": gen_lut, "loss": gen_loss, "supernet": gen_supernet, "supernet_l16": gen_supernet_l16,
+         "supernet_l16_batch": gen_supernet_l16_batch, "search_iter_l16": gen_search_iteration_l16, "eval": gen_eval, "student_step": gen_student_step, "trajectory": gen_optimizer_trajectory}[w]()
 
 
 if __name__ == "__main__":

@@ -52,6 +52,21 @@ def seeded_input(shape, seed=0):
     return torch.randn(shape, generator=g)
 
 
+def search_iteration_batch(it, shape):
+    """(imgs, target, imgs_search, target_search) of iteration `it` of the search-loop fixture (oracle/make_golden.py
+    gen_search_iteration_l16): distinct images and labels (1/8 resolution, ~5 % ignore = 255) for both steps and both iterations."""
+    out = []
+    for k in (0, 1):
+        base = 60 + 10 * it + 2 * k
+        x = seeded_input(shape, base)
+        g = torch.Generator().manual_seed(base + 1)
+        B, _, H, W = shape
+        target = torch.randint(0, 19, (B, H // 8, W // 8), generator=g)
+        target[torch.rand(target.shape, generator=g) < 0.05] = 255
+        out += [x, target]
+    return out
+
+
 def resolve_aliases(params, meta):
     """Shared cells appear under several state_dict keys (train/model_seg.py:293-294, e.g. cells.0-0.* and
     cells.0-1.* are ONE module).  nn.Module.load_state_dict writes every key, so the last alias wins; give

@@ -429,6 +429,63 @@ def test_shared_stem_of_a_pass_pair_equals_per_pass_stems(pretrain, use_graphs):
             assert float((ref_stats[k] - new_stats[k]).norm() / (ref_stats[k].norm() + 1e-9)) < 2e-2, k
 
 
+def _ohem_kept(pred, target, thresh, min_kept):
+    """(valid, kept) pixel counts of ProbOhemCrossEntropy2d's selection (loss_opr.py:70-93), restated in torch on the host."""
+    prob = torch.softmax(pred.detach().double().cpu(), 1)
+    t = target.cpu().reshape(-1)
+    valid = t.ne(255)
+    true_prob = prob.permute(1, 0, 2, 3).reshape(prob.shape[1], -1).gather(0, (t * valid).unsqueeze(0)).squeeze(0).masked_fill(~valid, 1)
+    threshold = max(thresh, float(torch.sort(true_prob).values[min(true_prob.numel(), min_kept) - 1]))
+    return int(valid.sum()), int((valid & true_prob.le(threshold)).sum())
+
+
+def test_joint_tail_with_a_per_call_criterion_equals_pass_by_pass(monkeypatch):
+    """The joint tail (forward_multi with batch_tails) returns the two passes' logits concatenated along the batch.  Pooling them into one
+    criterion call equals the sum of two calls only for plain mean cross-entropy; OHEM (the reference's supernet criterion,
+    train_search.py:62-66) selects pixels per call.  With losses.ProbOhemCrossEntropy2d on model._criterion, one eager pretrain step - both
+    pass pairs (max + min, random + random) through the joint tail - gives the loss and gradients of pass-by-pass evaluation
+    (_JOINT_PASSES = False) from the same seeds.  thresh / min_kept: at this initialisation every pixel's true-class probability is far
+    below the reference's 0.7 (median ~0.035), so that threshold keeps every pixel and pools like CE; with thresh 0.01 the selection is
+    made by min_kept (the 256 hardest of ~970 valid pixels per call), which pooling halves per pass."""
+    from fasterseg_amd import losses, model_search, train_step
+    thresh, min_kept = 0.01, 256
+    monkeypatch.setattr(model_search, "_TAIL_BATCH", True)
+
+    class Recording(losses.ProbOhemCrossEntropy2d):
+        def forward(self, pred, target):
+            self.calls.append((pred.detach().float().clone(), target.clone()))
+            return super().forward(pred, target)
+
+    cfg = type("Cfg", (SmallSearch,), dict(lr=0.0))
+    probes = ("stem.0.0.conv.0.weight", "cells.1.0._op._ops.3.conv1.weight", "cells.2.1.downsample._ops.4.bn2.bn.4.weight",
+              "head02.0.conv_1x1.weight", "head0.0.conv_1x1.bias")
+    res = {}
+    for joint in (False, True):
+        monkeypatch.setattr(train_step, "_JOINT_PASSES", joint)
+        st = train_step.SupernetStep(pretrain=True, cfg=cfg, seed=11, use_graphs=False)
+        st._prewarmed = True
+        assert [len(g) for g in st._groups()] == ([2, 2] if joint else [1, 1, 1, 1])
+        crit = Recording(ignore_label=255, thresh=thresh, min_kept=min_kept)
+        crit.calls = []
+        st.model._criterion = crit
+        imgs, tgt = _batch()
+        np.random.seed(21)
+        torch.manual_seed(21)
+        loss = float(st.step(imgs, tgt)[0])
+        params = dict(st.model.named_parameters())
+        res[joint] = (loss, {k: params[k].grad.detach().double().cpu().clone() for k in probes}, crit.calls)
+    (seq_loss, seq_g, seq_calls), (joint_loss, joint_g, joint_calls) = res[False], res[True]
+    assert len(seq_calls) == 20 and all(c[0].shape[0] == 2 for c in seq_calls)
+    for pred, target in seq_calls:                # OHEM is selecting: a proper subset of the valid pixels is kept, in every call
+        valid, kept = _ohem_kept(pred, target, thresh, min_kept)
+        assert min_kept <= kept < valid, (valid, kept)
+    assert abs(joint_loss - seq_loss) <= 1e-3 * abs(seq_loss), (joint_loss, seq_loss)
+    for k in probes:
+        rel = float((joint_g[k] - seq_g[k]).norm() / (seq_g[k].norm() + 1e-12))
+        assert rel < 2e-2, (k, rel)
+    assert len(joint_calls) == 20 and all(c[0].shape[0] == 2 for c in joint_calls), "the criterion saw the logits of two passes at once"
+
+
 @pytest.mark.parametrize("pretrain", [True, False], ids=["pretrain", "search"])
 def test_dp_overlap_bookkeeping_of_the_last_eager_group_changes_nothing(pretrain):
     """Under DP the gradient buckets leave under the backward of the step's last EAGER group (FlatGradientSync.final_pass; in the search
