@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfasterseg_hip.so")
 
-EXPECTED_ABI = 211          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
+EXPECTED_ABI = 212          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
 FS_F32, FS_BF16 = 0, 1
 FS_CONV_RELU, FS_CONV_TRANSPOSED, FS_CONV_ACCUM, FS_CONV_RELU_TAIL = 1, 2, 4, 8
 
@@ -33,6 +33,11 @@ class LogitsDesc(ctypes.Structure):
 
 class ResizeDesc(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("N", "Hi", "Wi", "Ho", "Wo", "C", "x_cs", "y_cs", "dtype", "relu", "out_nchw")]
+
+
+class EvalWindowDesc(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("H", "W", "rows", "cols", "top", "left", "oy", "ox", "crop_h", "crop_w", "pad_mode", "flip")] + [
+        ("mean", c_float * 3), ("std", c_float * 3)]
 
 
 class CensusEntry(ctypes.Structure):
@@ -66,6 +71,10 @@ SIGNATURES = {
     "fs_bilinear_fwd": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp],
     "fs_bilinear_argmax": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp],
     "fs_hist_info": [c_vp, c_vp, c_vp, c_int, c_ll, c_int, c_vp, c_vp],
+    "fs_eval_window_input": [c_vp, ctypes.POINTER(EvalWindowDesc), c_vp, c_vp, c_vp, c_vp],
+    "fs_eval_score_accumulate": [c_vp, ctypes.POINTER(LogitsDesc), c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
+                                 c_int, c_int, c_int, c_vp],
+    "fs_eval_rescale_accumulate": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp],
     "fs_bilinear_bwd": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp, c_vp],
     "fs_bilinear_bwd_nchw": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp, c_vp],
     "fs_bn_finalize": [c_vp, c_int, c_ll, c_vp, c_vp, c_vp, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -173,7 +182,7 @@ def lib():
         if got != EXPECTED_ABI:
             raise ImportError("libfasterseg_hip.so has ABI %d, these bindings expect %d: rebuild with `python -m fasterseg_amd.build "
                               "--force`" % (got, EXPECTED_ABI))
-        for which, struct in enumerate((ConvDesc, ResizeDesc, ZoomDesc, SgdTensor, LogitsDesc)):
+        for which, struct in enumerate((ConvDesc, ResizeDesc, ZoomDesc, SgdTensor, LogitsDesc, EvalWindowDesc)):
             if handle.fs_struct_size(which) != ctypes.sizeof(struct):
                 raise ImportError("libfasterseg_hip.so: sizeof(%s) is %d in the library, %d in the bindings - stale build" % (
                     struct.__name__, handle.fs_struct_size(which), ctypes.sizeof(struct)))

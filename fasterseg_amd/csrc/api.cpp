@@ -38,6 +38,7 @@ extern "C" int fs_struct_size(int which) {
         case 2: return (int)sizeof(fs_zoom_desc);
         case 3: return (int)sizeof(fs_sgd_tensor);
         case 4: return (int)sizeof(fs_logits_desc);
+        case 5: return (int)sizeof(fs_eval_window_desc);
         default: return -1;
     }
 }

@@ -1,29 +1,66 @@
-"""Validation path with the per-pixel work on the device (drop-in for the whole-image branch of the reference's
-tools/engine/evaluator.py Evaluator + train/eval.py SegEvaluator).
+"""Validation path with the per-pixel work on the device (drop-in for tools/engine/evaluator.py Evaluator + train/eval.py SegEvaluator).
 
 Reference, per validation image (evaluator.py:205-225, 297-318; eval.py:17-28): normalise on the host, forward, exp() of the
 (19, 1024, 2048) fp32 score map, copy 159 MB to the host, np.argmax, hist_info on the host.  Here: the image is normalised on
 the device, the network runs from the static-plan engine in class-map mode (the final x8 up-sample and the arg-max are one
 launch writing a 2 MB uint8 map), and the confusion histogram is accumulated on the device; the host reads 19 x 19 counts at
-the end of the run.  Multi-scale / sliding-window / flip evaluation (evaluator.py:227-295) need cv2 resampling of the input
-and are out of scope (config_train.py:67-68 uses a single scale without flip)."""
+the end of the run.
+
+Multi-scale, sliding-window and flip evaluation (evaluator.py:206-295; the eval_scale_array / eval_flip / eval_crop_size /
+eval_stride_rate config fields) run on the device too: per window, fs_eval_window_input builds the network input straight from
+the uint8 image (cv2's fixed-point bilinear resize, padding, normalisation, the mirrored copy), the engine runs in "lowres" mode,
+fs_eval_score_accumulate adds exp(l + unflip(l_flip)) of the x8 up-sampled logits into a per-scale canvas, and
+fs_eval_rescale_accumulate resizes each scale's canvas back to the image (cv2 INTER_LINEAR on float) into the total, taking the
+arg-max on the last scale.  The host only plans (fasterseg_amd.eval_plan) and issues launches."""
 import numpy as np
 import torch
 
 from . import engine
+from . import eval_plan as EP
+from . import kernels as K
 from .metric import HistAccumulator, compute_score
 
 
+class _ImageState:
+    """Device buffers of one image shape, allocated on its first frame and reused: the uploaded image, the fp32 HWC total and
+    the class map, one flat fp32 canvas (grown to the largest canvas a plan needs), the per-scale plans with their tap tables."""
+
+    def __init__(self, H, W, cs, device):
+        self.img = torch.empty((H, W, 3), dtype=torch.uint8, device=device)
+        self.total = torch.empty((H, W, cs), dtype=torch.float32, device=device)
+        self.classes = torch.empty((H, W), dtype=torch.uint8, device=device)
+        self.canvas = torch.empty(0, dtype=torch.float32, device=device)
+        self.plans = {}
+        self.outputs = {}
+
+
 class SegEvaluator:
-    def __init__(self, network, class_num, image_mean, image_std, image_shape=(1024, 2048), dtype=torch.bfloat16, device="cuda"):
+    def __init__(self, network, class_num, image_mean, image_std, image_shape=(1024, 2048), dtype=torch.bfloat16, device="cuda",
+                 multi_scales=(1,), is_flip=False, crop_size=None, stride_rate=5 / 6):
         self.class_num = class_num
         self.device = torch.device(device)
         self.image_mean = torch.tensor(np.asarray(image_mean, dtype=np.float32), device=self.device).view(1, 3, 1, 1)
         self.image_std = torch.tensor(np.asarray(image_std, dtype=np.float32), device=self.device).view(1, 3, 1, 1)
+        self._mean = [float(v) for v in np.asarray(image_mean, dtype=np.float32)]
+        self._std = [float(v) for v in np.asarray(image_std, dtype=np.float32)]
         H, W = image_shape
+        self.image_shape = (H, W)
+        self.dtype = dtype
+        self.multi_scales = list(multi_scales)
+        self.is_flip = bool(is_flip)
+        self.crop_size = crop_size
+        self.stride_rate = stride_rate
+        assert len(self.multi_scales) >= 1
+        assert len(self.multi_scales) == 1 or crop_size is not None, "multi-scale evaluation slides a crop_size window (eval_crop_size)"
         self.val_func = network.eval()
-        self.engine = engine.InferenceEngine(self.val_func, (1, 3, H, W), dtype=dtype, output="classes")
+        # the whole-image class-map engine of today's single-scale, no-flip path; built up front when that is the configured path
+        self.engine = None
+        if len(self.multi_scales) == 1 and not self.is_flip:
+            self.engine = engine.InferenceEngine(self.val_func, (1, 3, H, W), dtype=dtype, output="classes")
         self.acc = HistAccumulator(class_num, self.device)
+        self.cs = K.round_up(class_num, 4)          # fp32 canvas / total channel stride (19 -> 20)
+        self._lowres = {}                           # input shape -> "lowres" engine
+        self._states = {}                           # (H, W) -> _ImageState
 
     def process_image(self, img):
         """HWC uint8 (numpy or tensor, RGB like the reference after its BGR->RGB flip) -> normalised (1, 3, H, W) fp32 on the
@@ -34,15 +71,127 @@ class SegEvaluator:
 
     def val_func_process(self, input_data):
         """(1, 3, H, W) normalised image -> (H, W) uint8 class map on the device (argmax(exp(score)) = argmax(score))."""
+        if self.engine is None:
+            self.engine = engine.InferenceEngine(self.val_func, (1, 3) + tuple(input_data.shape[2:]), dtype=self.dtype, output="classes")
         return self.engine(input_data)[0]
 
+    # ---- device buffers and engines of the multi-scale / flip paths ------------------------------------------------------
+    def _lowres_engine(self, shape):
+        eng = self._lowres.get(shape)
+        if eng is None:
+            eng = self._lowres[shape] = engine.InferenceEngine(self.val_func, shape, dtype=self.dtype, output="lowres")
+        return eng
+
+    def _upload(self, img):
+        """The image as a contiguous uint8 (H, W, 3) device tensor (copied into the shape's buffer unless it already is one)."""
+        t = torch.as_tensor(img)
+        assert t.dim() == 3 and t.shape[2] == 3 and t.dtype == torch.uint8, "expected an HWC uint8 RGB image"
+        H, W = int(t.shape[0]), int(t.shape[1])
+        st = self._states.get((H, W))
+        if st is None:
+            st = self._states[(H, W)] = _ImageState(H, W, self.cs, self.device)
+        if t.is_cuda and t.is_contiguous():
+            return t, st
+        st.img.copy_(t)
+        return st.img, st
+
+    def _canvas(self, st, rows, cols):
+        n = rows * cols * self.cs
+        if st.canvas.numel() < n:
+            st.canvas = torch.empty(n, dtype=torch.float32, device=self.device)
+        return st.canvas[:n].view(rows, cols, self.cs)
+
+    def _plan(self, st, H, W, crop, stride_rate):
+        key = (tuple(self.multi_scales), int(crop), float(stride_rate))
+        plans = st.plans.get(key)
+        if plans is None:
+            plans = EP.scale_plan(H, W, self.multi_scales, crop, stride_rate)
+            for p in plans:
+                p.ytab = torch.from_numpy(EP.pack_taps(p.y_index, p.y_coef)).to(self.device)
+                p.xtab = torch.from_numpy(EP.pack_taps(p.x_index, p.x_coef)).to(self.device)
+                p.descs = [K.eval_window_desc(H, W, p.rows, p.cols, p.top, p.left, oy, ox, crop, crop, p.pad_mode, self.is_flip,
+                                              self._mean, self._std) for oy, ox in p.windows]
+                self._canvas(st, p.canvas_h, p.canvas_w)          # grow the canvas now, not in the frame loop
+            st.plans[key] = plans
+        return plans
+
+    def _identity_taps(self, st, H, W):
+        taps = st.plans.get("identity")
+        if taps is None:
+            taps = st.plans["identity"] = tuple(torch.from_numpy(EP.pack_taps(*EP.linear_taps(n, n, 1.0))).to(self.device) for n in (H, W))
+        return taps
+
+    # ---- evaluation modes ------------------------------------------------------------------------------------------------
     def whole_eval(self, img, output_size=None, input_size=None):
-        assert output_size is None and input_size is None, "resized / padded evaluation needs cv2 (out of scope)"
-        return self.val_func_process(self.process_image(img))
+        """evaluator.py:206-225: the whole image in one pass (plus its mirror with is_flip).  input_size: the normalised image
+        is padded with 0 to it (margins as pad_image_to_shape) and the score cropped back; output_size: the exp-score is
+        resized to it (cv2 INTER_LINEAR) before the arg-max.  Returns the uint8 class map on the device."""
+        if output_size is None and input_size is None and not self.is_flip:
+            return self.val_func_process(self.process_image(img))
+        img, st = self._upload(img)
+        H, W = int(img.shape[0]), int(img.shape[1])
+        ih, iw = EP.two_d(input_size) if input_size is not None else (H, W)
+        top, bottom, left, right = EP.pad_margins(H, W, ih, iw)
+        PH, PW = H + top + bottom, W + left + right
+        flip = self.is_flip
+        eng = self._lowres_engine((2 if flip else 1, 3, PH, PW))
+        ytab, xtab = self._identity_taps(st, H, W)
+        d = K.eval_window_desc(H, W, H, W, top, left, 0, 0, PH, PW, EP.PAD_NORMALISED, flip, self._mean, self._std)
+        K.eval_window_input(d, img, ytab, xtab, eng.input)
+        logits = eng.run()
+        rect = (top, left, H, W)
+        if output_size is None:
+            return K.eval_score_accumulate(logits, (PH, PW), flip, rect, classes=st.classes)
+        OH, OW = EP.two_d(output_size)
+        out = st.outputs.get((OH, OW))
+        if out is None:
+            out = st.outputs[(OH, OW)] = (torch.empty((OH, OW, self.cs), dtype=torch.float32, device=self.device),
+                                          torch.empty((OH, OW), dtype=torch.uint8, device=self.device))
+        canvas = self._canvas(st, H, W)
+        K.eval_score_accumulate(logits, (PH, PW), flip, rect, canvas=canvas, store=True)
+        K.eval_rescale_accumulate(canvas, self.class_num, (0, 0, H, W), out[0], store=True, classes=out[1])
+        return out[1]
+
+    def scale_process(self, img, plan, store, classes=None):
+        """evaluator.py:243-295 for one scale of `plan` (an eval_plan.ScalePlan of this image): every window's exp-score summed
+        on the scale's canvas, the score rectangle resized to the image and added into (store: written to) the image's fp32
+        total; with `classes`, the arg-max of the updated total is written there and returned, else the total."""
+        img, st = self._upload(img)
+        crop = plan.crop
+        flip = self.is_flip
+        eng = self._lowres_engine((2 if flip else 1, 3, crop, crop))
+        if plan.sliding:
+            canvas = self._canvas(st, plan.canvas_h, plan.canvas_w)
+            canvas.zero_()
+            for d in plan.descs:
+                K.eval_window_input(d, img, plan.ytab, plan.xtab, eng.input)
+                K.eval_score_accumulate(eng.run(), (crop, crop), flip, (0, 0, crop, crop), canvas=canvas, at=(d.oy, d.ox))
+            rect = (plan.top, plan.left, plan.rows, plan.cols)
+        else:
+            canvas = self._canvas(st, plan.rows, plan.cols)
+            K.eval_window_input(plan.descs[0], img, plan.ytab, plan.xtab, eng.input)
+            K.eval_score_accumulate(eng.run(), (crop, crop), flip, (plan.top, plan.left, plan.rows, plan.cols), canvas=canvas, store=True)
+            rect = (0, 0, plan.rows, plan.cols)
+        K.eval_rescale_accumulate(canvas, self.class_num, rect, st.total, store=store, classes=classes)
+        return st.total if classes is None else classes
+
+    def sliding_eval(self, img, crop_size, stride_rate):
+        """evaluator.py:228-241: the sum over self.multi_scales of scale_process, arg-max over the classes.  Returns the uint8
+        class map on the device; the summed score stays in the image's total buffer."""
+        img, st = self._upload(img)
+        H, W = int(img.shape[0]), int(img.shape[1])
+        plans = self._plan(st, H, W, crop_size, stride_rate)
+        for i, p in enumerate(plans):
+            self.scale_process(img, p, store=(i == 0), classes=st.classes if i == len(plans) - 1 else None)
+        return st.classes
 
     def func_per_iteration(self, data):
-        """data: {'data': HWC uint8 image, 'label': (H, W) labels}; accumulates on the device, returns the class map."""
-        pred = self.whole_eval(data['data'])
+        """data: {'data': HWC uint8 image, 'label': (H, W) labels}; accumulates on the device, returns the class map.
+        Dispatch of train/eval.py:23-26: one scale -> whole_eval (the scale value is not used), more -> sliding_eval."""
+        if len(self.multi_scales) == 1:
+            pred = self.whole_eval(data['data'])
+        else:
+            pred = self.sliding_eval(data['data'], self.crop_size, self.stride_rate)
         label = torch.as_tensor(data['label']).to(self.device)
         self.acc.add(pred, label.contiguous())
         return pred

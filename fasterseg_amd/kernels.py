@@ -549,6 +549,58 @@ def cat_channels(tensors):
     return out
 
 
+def eval_window_desc(H, W, rows, cols, top, left, oy, ox, crop_h, crop_w, pad_mode, flip, mean, std):
+    """fs_eval_window_desc: window (oy, ox) of the canvas holding the (rows, cols) resize of an (H, W) image at (top, left)."""
+    return _lib.EvalWindowDesc(H, W, rows, cols, top, left, oy, ox, crop_h, crop_w, pad_mode, int(flip),
+                               (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std]))
+
+
+def eval_window_input(d, img, ytab, xtab, out):
+    """fs_eval_window_input: uint8 (H, W, 3) image -> resized / padded / normalised window in out (1 + flip, 3, crop_h, crop_w) fp32.
+    ytab / xtab: int32 (rows, 2) / (cols, 2) tap tables (eval_plan.pack_taps)."""
+    assert img.dtype == torch.uint8 and img.is_contiguous() and tuple(img.shape) == (d.H, d.W, 3)
+    assert ytab.dtype == torch.int32 and tuple(ytab.shape) == (d.rows, 2) and xtab.dtype == torch.int32 and tuple(xtab.shape) == (d.cols, 2)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape[1:]) == (3, d.crop_h, d.crop_w) and out.shape[0] >= 1 + d.flip
+    call("fs_eval_window_input", _stream(), ctypes.byref(d), _p(img), _p(ytab.contiguous()), _p(xtab.contiguous()), _p(out))
+    return out
+
+
+def eval_score_accumulate(logits, size, flip, rect, canvas=None, at=(0, 0), store=False, classes=None):
+    """fs_eval_score_accumulate on the "lowres" engine output `logits` (N, C, h, w) NHWC view whose x8 up-sample is the window `size`:
+    over the window rectangle rect = (y0, x0, rows, cols), exp(l0 (+ l1 mirrored)) added (stored) into the fp32 HWC canvas
+    (Hc, Wc, cs) at `at`, or, with `classes` ((rows, cols) uint8), the arg-max of l0 (+ l1 mirrored)."""
+    N, C, h, w = logits.shape
+    cs = channel_stride(logits)
+    assert cs is not None, "logits must be an NHWC view"
+    d = _lib.LogitsDesc(N, h, w, C, cs, int(size[0]), int(size[1]), dtype_code(logits.dtype))
+    y0, x0, rows, cols = (int(v) for v in rect)
+    if classes is not None:
+        assert classes.dtype == torch.uint8 and classes.is_contiguous() and classes.numel() == rows * cols
+        call("fs_eval_score_accumulate", _stream(), ctypes.byref(d), _p(logits), int(flip), y0, x0, rows, cols, None, 0, 0, 0, 0, 0, 0,
+             _p(classes))
+        return classes
+    assert canvas.dtype == torch.float32 and canvas.is_contiguous() and canvas.dim() == 3
+    Hc, Wc, ccs = canvas.shape
+    call("fs_eval_score_accumulate", _stream(), ctypes.byref(d), _p(logits), int(flip), y0, x0, rows, cols, _p(canvas), Hc, Wc, ccs,
+         int(at[0]), int(at[1]), int(bool(store)), None)
+    return canvas
+
+
+def eval_rescale_accumulate(canvas, C, rect, total, store=False, classes=None):
+    """fs_eval_rescale_accumulate: total (H, W, cs) fp32 (+)= cv2 INTER_LINEAR resize of the canvas (Hc, Wc, cs) rectangle
+    rect = (y0, x0, rows, cols); with `classes` ((H, W) uint8) also the arg-max of the updated total over C classes."""
+    assert canvas.dtype == torch.float32 and canvas.is_contiguous() and canvas.dim() == 3
+    assert total.dtype == torch.float32 and total.is_contiguous() and total.dim() == 3 and total.shape[2] == canvas.shape[2]
+    Hc, Wc, cs = canvas.shape
+    H, W = total.shape[:2]
+    if classes is not None:
+        assert classes.dtype == torch.uint8 and classes.is_contiguous() and classes.numel() == H * W
+    y0, x0, rows, cols = (int(v) for v in rect)
+    call("fs_eval_rescale_accumulate", _stream(), _p(canvas), Hc, Wc, cs, int(C), y0, x0, rows, cols, _p(total), H, W, int(bool(store)),
+         _p(classes))
+    return total
+
+
 def deterministic_on():
     """Is the library in its bit-reproducible mode (fs_set_deterministic / FS_DETERMINISTIC=1)?"""
     return bool(_lib.lib().fs_get_deterministic())

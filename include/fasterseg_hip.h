@@ -88,7 +88,7 @@ typedef struct fs_resize_desc {
 const char* fs_last_error(void);
 /* ABI revision of this header; fs_version() returns the one the library was built from.  Bindings check both this and
  * fs_struct_size() when they load the library (fasterseg_amd/_lib.py) - a stale .so must not be used silently. */
-#define FS_ABI_VERSION 211
+#define FS_ABI_VERSION 212
 int fs_version(void);
 /* Bit-reproducible mode (default off; FS_DETERMINISTIC=1 in the environment turns it on at load): every cross-block reduction that
  * otherwise uses float atomics - the pixel slabs of fs_conv2d_wgrad_ws, BatchNorm statistics and parameter gradients of maps above
@@ -104,7 +104,8 @@ int fs_get_deterministic(void);
  * LDS-DMA kernel's tiles of 64 rows or channels and more) and fs_conv2d_wgrad*; everything else of the fp32 path is unchanged. */
 void fs_set_fp32_split(int on);
 int fs_get_fp32_split(void);
-int fs_struct_size(int which);   /* 0 fs_conv_desc, 1 fs_resize_desc, 2 fs_zoom_desc, 3 fs_sgd_tensor, 4 fs_logits_desc; -1 otherwise */
+int fs_struct_size(int which);   /* 0 fs_conv_desc, 1 fs_resize_desc, 2 fs_zoom_desc, 3 fs_sgd_tensor, 4 fs_logits_desc,
+                                    5 fs_eval_window_desc; -1 otherwise */
 /* test hook: force the tile configuration of fs_conv2d_fwd (0..7; -1 = heuristic).  Not for production use. */
 void fs_debug_force_conv_cfg(int cfg);
 /* number of elements of a packed filter bank for (Cout,R,S,Cin) */
@@ -516,6 +517,51 @@ enum {
     FS_OP_BN_UNIT_BWD,       /* fs_bn_act_train_bwd */
     FS_OP_COUNT
 };
+
+/* --- multi-scale / sliding-window / flip evaluation (ABI 212) ------------------------------------------------------ */
+/* One network input window of sliding_eval / scale_process / whole_eval(input_size=...) (tools/engine/evaluator.py:206-295):
+ * the uint8 image resized by cv2.resize(img, None, fx=s, fy=s, INTER_LINEAR) (8-bit fixed point, INTER_RESIZE_COEF_BITS = 11),
+ * placed at (top, left) of a padded canvas, the crop_h x crop_w window at (oy, ox) of that canvas, normalised
+ * (u / 255 - mean) / std in fp32 (img_utils.py:178-184).  Canvas pixels outside the resized image are the uint8 value 0 before
+ * normalisation (pad_mode 0: the sliding branch's pad_image_to_shape of the uint8 image, :256-257) or 0 after it (pad_mode 1:
+ * process_image(img, crop_size), :331-332).  flip = 1 also writes the window mirrored in x into batch slot 1 (:313). */
+typedef struct fs_eval_window_desc {
+    int H, W;               /* original image, uint8 HWC RGB                                        */
+    int rows, cols;         /* resized image: cvRound(H * s), cvRound(W * s)                        */
+    int top, left;          /* the resized image's origin in the padded canvas                      */
+    int oy, ox;             /* the window's origin in the padded canvas                             */
+    int crop_h, crop_w;     /* window = network input (1 + flip, 3, crop_h, crop_w); crop_w % 4 == 0 */
+    int pad_mode;           /* 0: uint8 0 before normalisation; 1: 0 after normalisation            */
+    int flip;               /* 1: the mirrored window into batch slot 1                            */
+    float mean[3], std[3];  /* per-channel normalisation                                            */
+} fs_eval_window_desc;
+/* Replaces cv2.resize + normalize + pad_image_to_shape + the slicing of evaluator.py:236-237,247-249,256-257,274-280 for one
+ * window.  ytab (rows entries) / xtab (cols entries) are int32 pairs [index, c0 | c1 << 16]: cv2's taps of each resized row /
+ * column, fx = (float)((d + 0.5) / s - 0.5), index = floor(fx) clamped to the image with fx = 0 at the edges,
+ * c = (cvRound((1 - fx) * 2048), cvRound(fx * 2048)) (fasterseg_amd/eval_plan.py builds them).  Per channel:
+ * D = S[index] * c0 + S[index + 1] * c1 along x, then (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2 along y.
+ * input: fp32 NCHW (1 + flip, 3, crop_h, crop_w), 16-byte aligned; every element of it is written. */
+fs_status fs_eval_window_input(void* stream, const fs_eval_window_desc* d, const unsigned char* img, const int* ytab, const int* xtab,
+                               float* input);
+/* val_func_process (evaluator.py:297-318) and the score accumulation of scale_process (:247-252, :281-290) from the engine's
+ * 1/8-resolution NHWC logits (d: N >= 1 + flip slots of h x w, channel stride cs; H x W = the window = the network input):
+ * the x8 align_corners=True up-sample of train/model_seg.py:365 evaluated per pixel (slot 1 at the mirrored column:
+ * score_flip.flip(-1)), l = l0 (+ l1), over the window rectangle [y0, y0 + rows) x [x0, x0 + cols).
+ * classes == NULL: canvas[cy + r, cx + c, k] = (store ? 0 : canvas[...]) + exp(l_k) on an fp32 HWC canvas (canvas_h x canvas_w,
+ * channel stride canvas_cs, a multiple of 4; pad channels get + 0, or 0 when storing).  classes != NULL: the uint8 arg-max of l
+ * (first maximum wins; C <= 256) into classes (rows x cols), the canvas is not touched (the single-scale flip path of whole_eval:
+ * argmax(exp(l)) = argmax(l)).  The windows of a scale are issued in order on one stream: no atomics, reproducible bits. */
+fs_status fs_eval_score_accumulate(void* stream, const fs_logits_desc* d, const void* logits, int flip, int y0, int x0, int rows,
+                                   int cols, float* canvas, int canvas_h, int canvas_w, int canvas_cs, int cy, int cx, int store,
+                                   unsigned char* classes);
+/* The per-scale cv2.resize(score, (W, H), INTER_LINEAR) of scale_process (evaluator.py:294-295) and of whole_eval(output_size=...)
+ * (:219-222) on float data, summed over the scales (sliding_eval :235-241): total[y, x, k] = (store ? 0 : total[...]) +
+ * resize(canvas rectangle [y0, y0 + rows) x [x0, x0 + cols)) with cv2's float taps (half-pixel centres, scale = in / out as
+ * 1 / (dsize / ssize), edge clamp, horizontal then vertical, no antialias).  canvas and total (H x W) are fp32 HWC with the
+ * same channel stride cs (a multiple of 4, >= C).  classes != NULL (the last scale): also the uint8 arg-max of the updated total
+ * over the C classes (np.argmax: first maximum wins; C <= 256). */
+fs_status fs_eval_rescale_accumulate(void* stream, const float* canvas, int canvas_h, int canvas_w, int cs, int C, int y0, int x0,
+                                     int rows, int cols, float* total, int H, int W, int store, unsigned char* classes);
 fs_status fs_exec_program(void* stream, const long long* words, long long n_words, const unsigned char* blob,
                           void* const* slots, int n_slots);
 /* Op word of every command: bits 0-15 the op code, bits 16-39 the stream lane (multi-stream form), bit 40 JOIN (ABI 208): this command
