@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfasterseg_hip.so")
 
-EXPECTED_ABI = 212          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
+EXPECTED_ABI = 213          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
 FS_F32, FS_BF16 = 0, 1
 FS_CONV_RELU, FS_CONV_TRANSPOSED, FS_CONV_ACCUM, FS_CONV_RELU_TAIL = 1, 2, 4, 8
 
@@ -38,6 +38,15 @@ class ResizeDesc(ctypes.Structure):
 class EvalWindowDesc(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("H", "W", "rows", "cols", "top", "left", "oy", "ox", "crop_h", "crop_w", "pad_mode", "flip")] + [
         ("mean", c_float * 3), ("std", c_float * 3)]
+
+
+class TrainSample(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("H", "W", "mirror", "sh", "sw", "pos_h", "pos_w", "top", "left", "rows", "cols", "ylin", "xlin",
+                                     "ynn", "xnn", "reserved")]
+
+
+class TrainBatchDesc(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("B", "crop_h", "crop_w", "g", "gy", "gx")] + [("n_tables", c_ll)]
 
 
 class CensusEntry(ctypes.Structure):
@@ -75,6 +84,8 @@ SIGNATURES = {
     "fs_eval_score_accumulate": [c_vp, ctypes.POINTER(LogitsDesc), c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
                                  c_int, c_int, c_int, c_vp],
     "fs_eval_rescale_accumulate": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp],
+    "fs_train_batch": [c_vp, ctypes.POINTER(TrainBatchDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "fs_resize_u8": [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int],
     "fs_bilinear_bwd": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp, c_vp],
     "fs_bilinear_bwd_nchw": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp, c_vp],
     "fs_bn_finalize": [c_vp, c_int, c_ll, c_vp, c_vp, c_vp, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -138,6 +149,7 @@ _SPECIAL = {
     "fs_sgd_chunk_elems": ([], c_int),
     "fs_sgd_tensor_chunks": ([c_ll, c_int, c_int, c_int], c_ll),
     "fs_loss_up_workspace_bytes": ([ctypes.POINTER(LogitsDesc)], c_ll),
+    "fs_train_batch_args_bytes": ([c_int], c_ll),
     "fs_zoom_cell_supported": ([ctypes.POINTER(ZoomDesc)], c_int),
     "fs_workspace_counter_bytes": ([], c_ll),
     "fs_set_deterministic": ([c_int], None),
@@ -182,7 +194,8 @@ def lib():
         if got != EXPECTED_ABI:
             raise ImportError("libfasterseg_hip.so has ABI %d, these bindings expect %d: rebuild with `python -m fasterseg_amd.build "
                               "--force`" % (got, EXPECTED_ABI))
-        for which, struct in enumerate((ConvDesc, ResizeDesc, ZoomDesc, SgdTensor, LogitsDesc, EvalWindowDesc)):
+        for which, struct in enumerate((ConvDesc, ResizeDesc, ZoomDesc, SgdTensor, LogitsDesc, EvalWindowDesc,
+                                           TrainSample, TrainBatchDesc)):
             if handle.fs_struct_size(which) != ctypes.sizeof(struct):
                 raise ImportError("libfasterseg_hip.so: sizeof(%s) is %d in the library, %d in the bindings - stale build" % (
                     struct.__name__, handle.fs_struct_size(which), ctypes.sizeof(struct)))

@@ -39,6 +39,8 @@ extern "C" int fs_struct_size(int which) {
         case 3: return (int)sizeof(fs_sgd_tensor);
         case 4: return (int)sizeof(fs_logits_desc);
         case 5: return (int)sizeof(fs_eval_window_desc);
+        case 6: return (int)sizeof(fs_train_sample);
+        case 7: return (int)sizeof(fs_train_batch_desc);
         default: return -1;
     }
 }

@@ -6,6 +6,7 @@ operands and torch.cat becomes "write into a slice".  torch is used only for mem
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -599,6 +600,40 @@ def eval_rescale_accumulate(canvas, C, rect, total, store=False, classes=None):
     call("fs_eval_rescale_accumulate", _stream(), _p(canvas), Hc, Wc, cs, int(C), y0, x0, rows, cols, _p(total), H, W, int(bool(store)),
          _p(classes))
     return total
+
+
+def train_batch(bd, samples, images, labels, tables, norm, staging, args, out_img, out_lbl):
+    """fs_train_batch: samples int32 (B, 16) host array of fs_train_sample rows, images / labels: B device uint8 tensors ((H, W, 3) /
+    (H, W)), tables int32 device tensor of bd.n_tables entries or more, norm (3, 256) fp32, staging / args: pinned host / device uint8
+    tensors of fs_train_batch_args_bytes(B) bytes or more -> out_img (B, 3, crop_h, crop_w) fp32, out_lbl (B, crop_h / g, crop_w / g)
+    int64.  The caller keeps `staging` untouched until the upload issued on the current stream has completed."""
+    B = bd.B
+    assert samples.dtype == np.int32 and samples.flags.c_contiguous and samples.shape == (B, 16) and len(images) == len(labels) == B
+    for im, lb, row in zip(images, labels, samples):
+        assert im.dtype == torch.uint8 and im.is_contiguous() and tuple(im.shape) == (int(row[0]), int(row[1]), 3), "bad source image"
+        assert lb.dtype == torch.uint8 and lb.is_contiguous() and tuple(lb.shape) == (int(row[0]), int(row[1])), "bad source label"
+    assert tables.dtype == torch.int32 and tables.numel() >= bd.n_tables and norm.dtype == torch.float32 and norm.numel() == 768
+    nbytes = _lib.lib().fs_train_batch_args_bytes(B)
+    assert staging.numel() >= nbytes and args.numel() >= nbytes and args.is_cuda and not staging.is_cuda
+    assert out_img.dtype == torch.float32 and out_img.is_contiguous() and tuple(out_img.shape) == (B, 3, bd.crop_h, bd.crop_w)
+    assert out_lbl.dtype == torch.int64 and out_lbl.is_contiguous() and tuple(out_lbl.shape) == (B, bd.crop_h // bd.g, bd.crop_w // bd.g)
+    ptrs = (ctypes.c_void_p * (2 * B))(*[t.data_ptr() for t in images], *[t.data_ptr() for t in labels])
+    call("fs_train_batch", _stream(), ctypes.byref(bd), samples.ctypes.data, ptrs, ctypes.addressof(ptrs) + B * ctypes.sizeof(ctypes.c_void_p),
+         _p(tables), _p(norm), ctypes.c_void_p(staging.data_ptr()), _p(args), _p(out_img), _p(out_lbl))
+    return out_img, out_lbl
+
+
+def resize_u8(src, out, ytab, xtab, nearest):
+    """fs_resize_u8: uint8 (H, W[, C]) -> out (h, w[, C]); linear: ytab / xtab int32 (h, 2) / (w, 2) taps, nearest: int32 (h,) / (w,)."""
+    assert src.dtype == torch.uint8 and src.is_contiguous() and out.dtype == torch.uint8 and out.is_contiguous()
+    assert src.dim() == out.dim() and src.dim() in (2, 3) and src.shape[2:] == out.shape[2:]
+    H, W = src.shape[:2]
+    h, w = out.shape[:2]
+    C = src.shape[2] if src.dim() == 3 else 1
+    assert ytab.dtype == torch.int32 and xtab.dtype == torch.int32
+    assert ytab.shape[0] == h and xtab.shape[0] == w and ytab.numel() == h * (1 if nearest else 2) and xtab.numel() == w * (1 if nearest else 2)
+    call("fs_resize_u8", _stream(), _p(src), H, W, C, _p(out), h, w, _p(ytab.contiguous()), _p(xtab.contiguous()), int(bool(nearest)))
+    return out
 
 
 def deterministic_on():

@@ -88,7 +88,7 @@ typedef struct fs_resize_desc {
 const char* fs_last_error(void);
 /* ABI revision of this header; fs_version() returns the one the library was built from.  Bindings check both this and
  * fs_struct_size() when they load the library (fasterseg_amd/_lib.py) - a stale .so must not be used silently. */
-#define FS_ABI_VERSION 212
+#define FS_ABI_VERSION 213
 int fs_version(void);
 /* Bit-reproducible mode (default off; FS_DETERMINISTIC=1 in the environment turns it on at load): every cross-block reduction that
  * otherwise uses float atomics - the pixel slabs of fs_conv2d_wgrad_ws, BatchNorm statistics and parameter gradients of maps above
@@ -105,7 +105,7 @@ int fs_get_deterministic(void);
 void fs_set_fp32_split(int on);
 int fs_get_fp32_split(void);
 int fs_struct_size(int which);   /* 0 fs_conv_desc, 1 fs_resize_desc, 2 fs_zoom_desc, 3 fs_sgd_tensor, 4 fs_logits_desc,
-                                    5 fs_eval_window_desc; -1 otherwise */
+                                    5 fs_eval_window_desc, 6 fs_train_sample, 7 fs_train_batch_desc; -1 otherwise */
 /* test hook: force the tile configuration of fs_conv2d_fwd (0..7; -1 = heuristic).  Not for production use. */
 void fs_debug_force_conv_cfg(int cfg);
 /* number of elements of a packed filter bank for (Cout,R,S,Cin) */
@@ -562,6 +562,52 @@ fs_status fs_eval_score_accumulate(void* stream, const fs_logits_desc* d, const 
  * over the C classes (np.argmax: first maximum wins; C <= 256). */
 fs_status fs_eval_rescale_accumulate(void* stream, const float* canvas, int canvas_h, int canvas_w, int cs, int C, int y0, int x0,
                                      int rows, int cols, float* total, int H, int W, int store, unsigned char* classes);
+/* --- training batches on the device (ABI 213) ------------------------------------------------------------------------ */
+/* The reference's TrainPre (search|train/dataloader.py) on one sample, after BaseDataset._open_image and the BGR -> RGB swap:
+ * random_mirror (cv2.flip(., 1) of image and label), random_scale (cv2.resize to (int(W * s), int(H * s)): INTER_LINEAR on the uint8
+ * image, INTER_NEAREST on the label), normalize ((u / 255.0 - mean) / std in float64, rounded to fp32), the crop at a random
+ * position and pad_image_to_shape (image padded with 0.0 after normalisation, label with 255), then the INTER_NEAREST label
+ * down-sample by gt_down_sampling g (tools/utils/img_utils.py).  fasterseg_amd/train_plan.py draws the sample and builds the tables. */
+typedef struct fs_train_sample {
+    int H, W;               /* source: uint8 HWC RGB image, uint8 HW label (already down-sampled at load)                   */
+    int mirror;             /* 1: the source is mirrored in x before the scale                                             */
+    int sh, sw;             /* scaled size int(H * s), int(W * s) (H, W without random_scale)                             */
+    int pos_h, pos_w;       /* crop origin in the scaled image                                                             */
+    int top, left;          /* pad margins above / left of the crop inside the crop_h x crop_w output                    */
+    int rows, cols;         /* valid rows / columns of the crop: min(crop, scaled - pos), >= 1                            */
+    int ylin, xlin;         /* int32 offsets in `tables` (even): cv2's linear taps of the scale, sh / sw pairs
+                               [index, c0 | c1 << 16] (the layout of fs_eval_window_input's ytab / xtab)                    */
+    int ynn, xnn;           /* int32 offsets in `tables`: cv2's INTER_NEAREST source indices of the scale, sh / sw entries   */
+    int reserved;           /* 0 */
+} fs_train_sample;
+typedef struct fs_train_batch_desc {
+    int B;                  /* samples, 1..65535                                                                            */
+    int crop_h, crop_w;     /* image_height, image_width; crop_w % 4 == 0                                                  */
+    int g;                  /* gt_down_sampling: divides crop_h and crop_w                                                  */
+    int gy, gx;             /* int32 offsets in `tables`: INTER_NEAREST indices of the label down-sample (crop_h / g, crop_w / g
+                               entries, positions in the padded crop)                                                       */
+    long long n_tables;     /* int32 entries in `tables`: every offset and length is checked against it                     */
+} fs_train_batch_desc;
+/* One launch builds the whole batch: out_img fp32 NCHW (B, 3, crop_h, crop_w) (16-byte aligned) and out_lbl int64
+ * (B, crop_h / g, crop_w / g) (16-byte aligned when crop_w / g is even, else 8).  samples, images and labels are HOST arrays of B
+ * entries (images[b] / labels[b]: device pointers to sample b's H x W x 3 / H x W uint8 source); they are validated, packed into
+ * `staging` (host memory of fs_train_batch_args_bytes(B) bytes, pinned for an asynchronous upload) and copied to `args` (device memory
+ * of the same size) on `stream` before the launch: the caller must not reuse `staging` until that copy has completed (an event after
+ * the call).  tables: the int32 tables of every sample and of the label down-sample; norm: 3 x 256 fp32, norm[c * 256 + u] = the
+ * normalised value of channel c for the uint8 value u.  Per output pixel the device only adds, compares and mirrors integers:
+ * image (y, x) = norm[resize_u8(taps of scaled row pos_h + y - top, column pos_w + x - left)] inside the crop, 0.0 outside;
+ * label (j, i) = the label at the nearest indices of scaled (pos_h + gy[j] - top, pos_w + gx[i] - left) inside the crop, 255 outside.
+ * A mirrored sample reads source column W - 1 - k for each tap index k (both taps).  Every output element is written. */
+fs_status fs_train_batch(void* stream, const fs_train_batch_desc* d, const fs_train_sample* samples, const unsigned char* const* images,
+                         const unsigned char* const* labels, const int* tables, const float* norm, void* staging, void* args,
+                         float* out_img, long long* out_lbl);
+/* Bytes of fs_train_batch's staging / argument block for B samples (0 for B < 1). */
+long long fs_train_batch_args_bytes(int B);
+/* BaseDataset._open_image's down-sampling at load: src (H x W x C uint8, C <= 4) -> dst (h x w x C uint8), mode 0: cv2 INTER_LINEAR
+ * with the 8-bit taps ytab / xtab (h / w int32 pairs as above), mode 1: INTER_NEAREST with the source indices ytab / xtab (h / w
+ * int32).  dst must not overlap src. */
+fs_status fs_resize_u8(void* stream, const unsigned char* src, int H, int W, int C, unsigned char* dst, int h, int w, const int* ytab,
+                       const int* xtab, int mode);
 fs_status fs_exec_program(void* stream, const long long* words, long long n_words, const unsigned char* blob,
                           void* const* slots, int n_slots);
 /* Op word of every command: bits 0-15 the op code, bits 16-39 the stream lane (multi-stream form), bit 40 JOIN (ABI 208): this command
