@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfasterseg_hip.so")
 
-EXPECTED_ABI = 213          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
+EXPECTED_ABI = 214          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
 FS_F32, FS_BF16 = 0, 1
 FS_CONV_RELU, FS_CONV_TRANSPOSED, FS_CONV_ACCUM, FS_CONV_RELU_TAIL = 1, 2, 4, 8
 
@@ -49,6 +49,13 @@ class TrainBatchDesc(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("B", "crop_h", "crop_w", "g", "gy", "gx")] + [("n_tables", c_ll)]
 
 
+FS_MAX_HEADS = 8
+
+
+class HeadsDesc(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("K", "N", "h", "w", "C", "H", "W", "dtype")] + [("cs", c_int * FS_MAX_HEADS)]
+
+
 class CensusEntry(ctypes.Structure):
     _fields_ = [("family", c_int), ("desc", ConvDesc), ("count", c_ll), ("ms", ctypes.c_double)]
 
@@ -80,6 +87,7 @@ SIGNATURES = {
     "fs_bilinear_fwd": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp],
     "fs_bilinear_argmax": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp],
     "fs_hist_info": [c_vp, c_vp, c_vp, c_int, c_ll, c_int, c_vp, c_vp],
+    "fs_heads_confusion": [c_vp, ctypes.POINTER(HeadsDesc), c_vp, c_vp, c_int, c_vp, c_vp],
     "fs_eval_window_input": [c_vp, ctypes.POINTER(EvalWindowDesc), c_vp, c_vp, c_vp, c_vp],
     "fs_eval_score_accumulate": [c_vp, ctypes.POINTER(LogitsDesc), c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
                                  c_int, c_int, c_int, c_vp],
@@ -195,7 +203,7 @@ def lib():
             raise ImportError("libfasterseg_hip.so has ABI %d, these bindings expect %d: rebuild with `python -m fasterseg_amd.build "
                               "--force`" % (got, EXPECTED_ABI))
         for which, struct in enumerate((ConvDesc, ResizeDesc, ZoomDesc, SgdTensor, LogitsDesc, EvalWindowDesc,
-                                           TrainSample, TrainBatchDesc)):
+                                           TrainSample, TrainBatchDesc, HeadsDesc)):
             if handle.fs_struct_size(which) != ctypes.sizeof(struct):
                 raise ImportError("libfasterseg_hip.so: sizeof(%s) is %d in the library, %d in the bindings - stale build" % (
                     struct.__name__, handle.fs_struct_size(which), ctypes.sizeof(struct)))

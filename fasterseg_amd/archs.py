@@ -24,10 +24,17 @@ def load_arch(idx):
     return {k: (torch.tensor(raw[k]) if raw[k].ndim else float(raw[k])) for k in raw.files}
 
 
-def build_derived(idx, training=False, lasts=None, num_classes=19, layers=16, Fch=12):
+def arch_from_state(state):
+    """An `arch_{idx}.pt` dict as torch.load returns it (search_eval.save_arch, train_search.py:185-202: tensors or parameters,
+    possibly on the GPU, and Python floats) in load_arch's form: detached host tensors and floats."""
+    return {k: (v.detach().cpu() if torch.is_tensor(v) else float(v)) for k, v in state.items()}
+
+
+def build_derived(idx, training=False, lasts=None, num_classes=19, layers=16, Fch=12, state=None):
     """Network_Multi_Path_Infer for arch `idx` (0 teacher, 1 student) as train/train.py:92-107 builds it: the last
-    layers are chosen by objective_acc_lat unless `lasts` is given; teacher ignores 'skip' (ignore_skip=True)."""
-    a = load_arch(idx)
+    layers are chosen by objective_acc_lat unless `lasts` is given; teacher ignores 'skip' (ignore_skip=True).
+    state: a loaded `arch_{idx}.pt` dict of a search (train.py:91-94) instead of the shipped architecture."""
+    a = load_arch(idx) if state is None else arch_from_state(state)
     net = Network_Multi_Path_Infer(
         [a["alpha_%d_0" % idx], a["alpha_%d_1" % idx], a["alpha_%d_2" % idx]],
         [None, a["beta_%d_1" % idx], a["beta_%d_2" % idx]],

@@ -29,6 +29,7 @@ HBM_FAMILIES = {
                                     "bn_fwd_mixed", "bn_bwd_mixed"),          # (the mixed group launches of round 6 carry most of the family)
     "bilinear resample": ("bilinear_fwd", "bilinear_bwd"),
     "weighted sums / axpy": ("wsum", "wsum_bwd", "wsum_dot", "ew"),
+    "eval heads confusion": ("heads_confusion", "heads_confusion8"),     # supernet validation (search_eval.py), not a train-step kernel
 }
 
 

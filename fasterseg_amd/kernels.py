@@ -602,6 +602,34 @@ def eval_rescale_accumulate(canvas, C, rect, total, store=False, classes=None):
     return total
 
 
+def heads_confusion(heads, gt, hist, counts):
+    """fs_heads_confusion: K <= 8 low-resolution heads (N, C, h, w) NHWC views of one dtype and geometry, each bilinearly up-sampled
+    (align_corners=True) to the labels' (H, W) and arg-maxed, counted into hist (K, C, C) / (K * C * C) and counts (K, 2) / (2 K)
+    int64 accumulators on the device: hist[k, gt, pred] += 1, counts[k] += (labeled, correct).  gt: (N, H, W) or (H, W) uint8 /
+    int32 / int64 labels (255, -1 or >= C: ignored)."""
+    heads = list(heads)
+    K = len(heads)
+    assert 1 <= K <= _lib.FS_MAX_HEADS, "1..%d heads" % _lib.FS_MAX_HEADS
+    N, C, h, w = heads[0].shape
+    cs = []
+    for t in heads:
+        assert tuple(t.shape) == (N, C, h, w) and t.dtype == heads[0].dtype and t.is_cuda, "the heads must share shape, dtype and device"
+        c = channel_stride(t)
+        assert c is not None, "heads must be NHWC views"
+        cs.append(c)
+    gt_bytes = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}.get(gt.dtype)
+    assert gt_bytes is not None, "labels must be uint8, int32 or int64, got %s" % gt.dtype
+    assert gt.is_cuda and gt.is_contiguous() and ((gt.dim() == 3 and gt.shape[0] == N) or (gt.dim() == 2 and N == 1)), \
+        "labels: (N, H, W), or (H, W) for N = 1"
+    H, W = int(gt.shape[-2]), int(gt.shape[-1])
+    for t, n in ((hist, K * C * C), (counts, 2 * K)):
+        assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and t.numel() == n, "accumulators: int64, contiguous"
+    d = _lib.HeadsDesc(K, N, h, w, C, H, W, dtype_code(heads[0].dtype), (ctypes.c_int * _lib.FS_MAX_HEADS)(*cs))
+    ptrs = (ctypes.c_void_p * K)(*[t.data_ptr() for t in heads])
+    call("fs_heads_confusion", _stream(), ctypes.byref(d), ptrs, _p(gt), gt_bytes, _p(hist), _p(counts))
+    return hist, counts
+
+
 def train_batch(bd, samples, images, labels, tables, norm, staging, args, out_img, out_lbl):
     """fs_train_batch: samples int32 (B, 16) host array of fs_train_sample rows, images / labels: B device uint8 tensors ((H, W, 3) /
     (H, W)), tables int32 device tensor of bd.n_tables entries or more, norm (3, 256) fp32, staging / args: pinned host / device uint8

@@ -642,6 +642,24 @@ class Network_Multi_Path(LatencyModelMixin, nn.Module):
         except StopIteration as done:
             return done.value
 
+    def forward_lowres(self, input):
+        """Eval mode: the five heads of `_tail` BEFORE their x8 up-sample, as (N, C, h, w) NHWC views of zero-padded logits buffers
+        (functional.CLS_PAD) - what search_eval.SupernetEvaluator hands to fs_heads_confusion.  `forward` is this followed by
+        FN.interpolate(p, scale_factor=8, out_nchw=1) per head."""
+        assert not self.training, "forward_lowres is the eval-mode forward"
+        global _SAMPLING_PASS
+        sampling = _SAMPLING_PASS           # a validation between train steps leaves the steps' module state as it found it
+        gen = self._forward_steps(input, defer_tail=True)
+        try:
+            tasks, dest_fn, _ = next(gen)
+            while True:
+                tasks, dest_fn, _ = gen.send(_run_tasks(tasks, dest_fn))
+        except StopIteration as done:
+            t = done.value
+        finally:
+            _SAMPLING_PASS = sampling
+        return self._heads(t.k, t.o0, t.o1, t.o2)
+
     def forward_multi(self, input, specs, batch_tails=False):
         """Several passes of `_loss` (reference :392-411: the same batch through the supernet once per width mode) evaluated TOGETHER,
         layer by layer: the MixedOp evaluations of all passes at one layer only depend on the previous layer of their own pass, so they
@@ -849,8 +867,8 @@ class Network_Multi_Path(LatencyModelMixin, nn.Module):
             return _DeferredTail(k, out[0][0], out[1][0], out[2][0])
         return self._tail(k, out[0][0], out[1][0], out[2][0])
 
-    def _tail(self, k, o0, o1, o2):
-        """Refinement + the five heads (reference forward :335-353) on the last layer's three maps."""
+    def _heads(self, k, o0, o1, o2):
+        """Refinement + the five heads (reference forward :335-352) on the last layer's three maps: their low-resolution logits."""
         refine16, refine32 = self.refine16[k], self.refine32[k]
         ###################################
         up2 = lambda t: FN.interpolate(t, scale_factor=2)
@@ -859,8 +877,12 @@ class Network_Multi_Path(LatencyModelMixin, nn.Module):
         out2 = refine32[1](FN.cat([up2(refine32[0](o2)), o1]))
         out2 = refine32[3](FN.cat([up2(refine32[2](out2)), o0]))
 
-        preds = [self.head0[k](out0), self.head1[k](out1), self.head2[k](out2),
-                 self.head02[k](FN.cat([out0, out2])), self.head12[k](FN.cat([out1, out2]))]
+        return [self.head0[k](out0), self.head1[k](out1), self.head2[k](out2),
+                self.head02[k](FN.cat([out0, out2])), self.head12[k](FN.cat([out1, out2]))]
+
+    def _tail(self, k, o0, o1, o2):
+        """Refinement + the five heads (reference forward :335-353) on the last layer's three maps."""
+        preds = self._heads(k, o0, o1, o2)
         if not self.training:
             return tuple(FN.interpolate(p, scale_factor=8, out_nchw=1) for p in preds)
         # train mode: 1/8-resolution logits (labels are down-sampled x8, search/dataloader.py:25); hand the loss a

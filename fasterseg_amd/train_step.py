@@ -18,12 +18,14 @@ from .parallel import FlatGradientSync, broadcast_parameters
 
 class StudentDistillStep:
     def __init__(self, batch, height, width, lr=0.01, momentum=0.9, weight_decay=5e-4, teacher_engine_dtype=None, seed=12345,
-                 device="cuda", compute_dtype=torch.float32, fused_loss=None):
+                 device="cuda", compute_dtype=torch.float32, fused_loss=None, arch_states=None):
         self.device = torch.device(device)
         self.compute_dtype = compute_dtype      # activation storage / MFMA operand type; master weights, BN statistics,
         # accumulators and gradients of parameters stay fp32
-        self.teacher = archs.init_weight(archs.build_derived(0, training=True), seed).to(self.device).eval()
-        self.student = archs.init_weight(archs.build_derived(1, training=True), seed + 1).to(self.device).train()
+        # arch_states: (teacher, student) `arch_{idx}.pt` dicts of a search (search_eval.save_arch) instead of the shipped architectures
+        st_t, st_s = arch_states if arch_states is not None else (None, None)
+        self.teacher = archs.init_weight(archs.build_derived(0, training=True, state=st_t), seed).to(self.device).eval()
+        self.student = archs.init_weight(archs.build_derived(1, training=True, state=st_s), seed + 1).to(self.device).train()
         broadcast_parameters(self.student)
         broadcast_parameters(self.teacher)
         min_kept = int(batch * height * width // 16)                       # train/train.py:62 with gt_down_sampling = 1

@@ -88,7 +88,7 @@ typedef struct fs_resize_desc {
 const char* fs_last_error(void);
 /* ABI revision of this header; fs_version() returns the one the library was built from.  Bindings check both this and
  * fs_struct_size() when they load the library (fasterseg_amd/_lib.py) - a stale .so must not be used silently. */
-#define FS_ABI_VERSION 213
+#define FS_ABI_VERSION 214
 int fs_version(void);
 /* Bit-reproducible mode (default off; FS_DETERMINISTIC=1 in the environment turns it on at load): every cross-block reduction that
  * otherwise uses float atomics - the pixel slabs of fs_conv2d_wgrad_ws, BatchNorm statistics and parameter gradients of maps above
@@ -105,7 +105,8 @@ int fs_get_deterministic(void);
 void fs_set_fp32_split(int on);
 int fs_get_fp32_split(void);
 int fs_struct_size(int which);   /* 0 fs_conv_desc, 1 fs_resize_desc, 2 fs_zoom_desc, 3 fs_sgd_tensor, 4 fs_logits_desc,
-                                    5 fs_eval_window_desc, 6 fs_train_sample, 7 fs_train_batch_desc; -1 otherwise */
+                                    5 fs_eval_window_desc, 6 fs_train_sample, 7 fs_train_batch_desc, 8 fs_heads_desc;
+                                    -1 otherwise */
 /* test hook: force the tile configuration of fs_conv2d_fwd (0..7; -1 = heuristic).  Not for production use. */
 void fs_debug_force_conv_cfg(int cfg);
 /* number of elements of a packed filter bank for (Cout,R,S,Cin) */
@@ -423,6 +424,29 @@ fs_status fs_bilinear_argmax(void* stream, const fs_resize_desc* d, const void* 
  * once per evaluation run.  Integer atomics: bit-exact with np.bincount. */
 fs_status fs_hist_info(void* stream, const unsigned char* pred, const void* gt, int gt_bytes, long long n, int n_cl,
                        unsigned long long* hist, unsigned long long* counts);
+
+/* --- supernet validation: several heads -> confusion histograms in one launch (ABI 214) ------------------------- */
+/* The five heads of one supernet forward (search/model_search.py _tail, before their x8 up-sample) evaluated as the reference's
+ * five evaluator sweeps do (search/train_search.py:259-271, tools/engine/evaluator.py:297-318, tools/seg_opr/metric.py:7-17), from
+ * ONE forward: per output pixel and head k, the align_corners=True bilinear up-sample of head k to (H, W) (fs_bilinear_argmax's
+ * taps and expression), its arg-max over the C classes (first maximum wins) and, when 0 <= gt < C (255 / -1 / >= C: ignored),
+ * hist[k * C * C + C * gt + pred] += 1, counts[2k] += 1 (labeled), counts[2k + 1] += (pred == gt) (correct): what
+ * fs_bilinear_argmax + fs_hist_info give head by head, bit for bit.  Nothing else is written. */
+#define FS_MAX_HEADS 8
+typedef struct fs_heads_desc {
+    int K;                  /* heads, 1..FS_MAX_HEADS                                               */
+    int N, h, w;            /* low-resolution logits of every head: (N, h, w, C) NHWC               */
+    int C;                  /* classes, 1..32                                                       */
+    int H, W;               /* output = label size                                                  */
+    int dtype;              /* fs_dtype of every head                                               */
+    int cs[FS_MAX_HEADS];   /* channel stride of head k: a multiple of 4, >= round_up(C, 4); pad lanes readable */
+} fs_heads_desc;
+/* heads: HOST array of K device pointers; gt: (N, H, W) uint8 / int32 / int64 (gt_bytes 1 / 4 / 8); hist (K * C * C) and counts
+ * (K * 2) are uint64 accumulators the caller zeroes once per run.  Per-block LDS counts flushed with integer atomics (no float
+ * atomics): the result does not depend on the order of arrival.  W == 8 * w (w >= 2) with C <= 20 takes the 1 x 8 strip
+ * kernel. */
+fs_status fs_heads_confusion(void* stream, const fs_heads_desc* d, const void* const* heads, const void* gt, int gt_bytes,
+                             unsigned long long* hist, unsigned long long* counts);
 
 /* --- launch census + in-step kernel timing (measurement support) ----------------------------------- */
 /* Level 1: every convolution launched through this ABI is counted by geometry (family + descriptor); launches issued during
