@@ -99,7 +99,11 @@ class InferenceEngine:
         # written to <file>.<output> after a build that timed them and read back by later builds instead of timing (a plan
         # tuned on an idle device can be replayed under a profiler, whose counters perturb the timings it would otherwise tune on)
         self._plan_path = os.environ.get("FS_ENGINE_PLAN")
-        self._plan_in, self._plan_out = None, {"convs": [], "cells": []}
+        self._plan_in, self._plan_out = None, {"convs": [], "cells": [], "folds": []}
+        # a 1/2 (or x2) resample whose only reader is a 3x3 / stride-1 conv can be folded into that conv's LDS-halo staging
+        # (fs_conv_desc.vr_* on fs_conv3x3_s1_fwd): "auto" (default) = per resample, whichever is faster in the frame; 0 never; 1 always
+        self.fold_resizes = os.environ.get("FS_ENGINE_FOLD_RESIZE", "auto")
+        self.fold_log = []
         self._trace(net)
         if self._plan_path:
             # a plan is replayed by position, so it is only valid for the network and input it was tuned on: its file name and
@@ -112,21 +116,23 @@ class InferenceEngine:
             if os.path.exists(self._plan_path):
                 with open(self._plan_path) as f:
                     plan = json.load(f)
-                if plan.get("signature") == sig:
+                if plan.get("signature") == sig and "folds" in plan:
                     self._plan_in = plan
         self._fuse_cells()
         self._fuse_resizes()
+        self._mark_halo_folds()
         self._assign_buffers()
         self._lower()
         self.graph = None
         if use_graph:
-            if self.fuse_cells == "auto" and self._plan_in is None:
+            if self._plan_in is None and any(len(g["variants"]) > 1 for g in self.groups):
                 self._warm()
                 self._tune_cells()
             self._capture()
         if self._plan_path and self._plan_in is None:
             import json
-            self._plan_out["cells"] = [g["choice"] for g in self.groups if len(g["variants"]) > 1]
+            self._plan_out["cells"] = [g["choice"] for g in self.groups if len(g["variants"]) > 1 and g["kind"] == "zoom"]
+            self._plan_out["folds"] = [g["choice"] for g in self.groups if len(g["variants"]) > 1 and g["kind"] != "zoom"]
             with open(self._plan_path, "w") as f:
                 json.dump(self._plan_out, f)
 
@@ -282,6 +288,28 @@ class InferenceEngine:
             rop["dead"] = True
             self.fused_resizes += 1
 
+    # ---- 1c. resamples that the LDS-halo 3x3 kernel can interpolate while it stages its input --------------------------
+    def _mark_halo_folds(self):
+        """`_fuse_resizes` leaves a resample in front of a 3x3 conv alone, rightly for the implicit GEMM (it would interpolate per
+        tap).  The halo kernel stages every input pixel once per channel chunk, so there the fold costs four source reads per staged
+        pixel and saves a launch and the round trip of the resampled map.  Candidates only: `_lower` builds both forms and
+        `_tune_cells` keeps the fold where the frame gets faster."""
+        self.halo_folds = 0
+        if self.fold_resizes in ("0", "off"):
+            return
+        consumers = self._consumers()
+        for rop in self.ops:
+            if rop["kind"] != "resize" or rop["out_nchw"] or rop["out"] is self.out_sym or rop.get("dead"):
+                continue
+            cons = consumers.get(rop["out"].id, [])
+            if len(cons) != 1:
+                continue
+            cop = self.ops[cons[0]]
+            if (cop["kind"] == "conv" and cop["k"] == 3 and cop["stride"] == 1 and cop["pad"] == 1 and cop.get("vres") is None
+                    and cop["x"] is rop["out"]):
+                cop["fold"] = rop
+                self.halo_folds += 1
+
     # ---- 2. buffers: one NHWC buffer per feature map; cat operands alias slices of the cat buffer ------
     def _new_buffer(self, N, H, W, cs, zero=False):
         make = torch.zeros if zero else torch.empty
@@ -355,15 +383,16 @@ class InferenceEngine:
         self._keep += [scale, shift]
         return scale, shift
 
-    def _add_conv(self, x, out, weight, scale, shift, k, stride, pad, relu, cout, cin, out_off=0, label="conv", vres=None):
+    def _add_conv(self, x, out, weight, scale, shift, k, stride, pad, relu, cout, cin, out_off=0, label="conv", vres=None, vres_halo=False):
         N, _, H, W = x.shape
         src_hw = None
         if vres is not None:                      # x is the un-resampled source; the conv reads its (H, W) resampling
             src_hw, (H, W) = (H, W), vres[:2]
             label = "%s[<-%dx%d%s]" % (label, src_hw[0], src_hw[1], "+relu" if vres[2] else "")
         _, _, Ho, Wo = out.shape
-        halo_ok = k == 3 and stride in (1, 2) and pad == 1 and vres is None
-        use_halo = halo_ok and stride == 1 and N * H * W >= self.halo_min_pixels
+        # vres_halo: the resample is folded into the halo kernel's staging (stride 1; the implicit GEMM is no candidate then)
+        halo_ok = k == 3 and stride in (1, 2) and pad == 1 and (vres is None or (vres_halo and stride == 1))
+        use_halo = halo_ok and stride == 1 and (N * H * W >= self.halo_min_pixels or vres_halo)
         xp, x_cs = self._ptr(x)
         yp, y_cs = self._ptr(out)
         yp += out_off * (2 if self.dtype == torch.bfloat16 else 4)
@@ -372,13 +401,15 @@ class InferenceEngine:
             d.vr_H, d.vr_W, d.vr_relu = src_hw[0], src_hw[1], int(vres[2])
         self._keep.append(d)
 
-        def variant(halo, tile=0):
+        def variant(halo, tile=0, ksplit=None):
             dd = d
-            if halo:        # LDS-halo 3x3 kernel with the fragment-packed filter bank; tile = forced output-channel tile (0: heuristic)
+            if halo:        # LDS-halo 3x3 kernel with the fragment-packed filter bank; tile = forced output-channel tile (0: heuristic),
+                            # ksplit = True / 16 / False: the K-split form (32- / 16-channel tiles) forced / forbidden (None: the library's rule)
                 wp = K.pack_weight_frag(weight.detach().to(self.device), self.dtype, cout, cin)
-                if tile:
+                if tile or ksplit is not None:
                     dd = ConvDesc.from_buffer_copy(bytes(d))
-                    dd.flags |= {32: 0x1000, 64: 0x2000, 128: 0x3000}[tile]
+                    dd.flags |= {0: 0, 32: 0x1000, 64: 0x2000, 128: 0x3000}[tile]
+                    dd.flags |= 0 if ksplit is None else (_lib.FS_CONV_KSPLIT16 if ksplit == 16 else _lib.FS_CONV_KSPLIT if ksplit else _lib.FS_CONV_NO_KSPLIT)
                     self._keep.append(dd)
             else:
                 wp = K.pack_weight(weight.detach().to(self.device), self.dtype, cout, cin)
@@ -389,14 +420,19 @@ class InferenceEngine:
         # how many blocks each gives on this map: every candidate is timed on the device at build and the fastest kept
         # (FS_ENGINE_AUTOTUNE=0: the heuristics only).
         if halo_ok and self.autotune and N * Ho * Wo >= 512:
-            cands = [("halo", variant(True)), ("igemm", variant(False))]
+            # "halo": the plain form with the heuristic tile, "halo32/64/128": a forced tile, "halo_ks" / "halo_ks16": the K-split form with 32- / 16-channel tiles (stride 1)
+            cands = [("halo", variant(True, ksplit=False))] + ([] if vres is not None else [("igemm", variant(False))])
             cands += [("halo%d" % t, variant(True, t)) for t in (32, 64, 128) if t <= max(32, K.round_up(cout, 32)) * 2 and t <= 128]
+            if stride == 1:
+                cands += [("halo_ks", variant(True, ksplit=True)), ("halo_ks16", variant(True, ksplit=16))]
             if self._plan_in is not None:
                 want = self._plan_in["convs"][len(self._plan_out["convs"])]
                 best = (0.0, want, dict(cands)[want])
                 timed = []
             else:
-                timed = [(self._time_call(v[0], v[1]), name, v) for name, v in cands]
+                # the implicit GEMM is timed as it will run: `_finish_lanes` hands it a split-K workspace (fs_conv2d_fwd_ws)
+                timed = [(self._time_call(v[0], v[1]) if name != "igemm" else self._time_call("fs_conv2d_fwd_ws", v[1] + self._tune_ws()), name, v)
+                         for name, v in cands]
                 best = min(timed, key=lambda tv: tv[0])
             self._plan_out["convs"].append(best[1])
             self.autotuned.append((label, N * H * W, cin, cout, best[1], [(nm, round(t * 1e3, 2)) for t, nm, _ in timed]))
@@ -408,6 +444,14 @@ class InferenceEngine:
         nbytes = es * (in_px * cin + cout * cin * k * k + N * Ho * Wo * cout)
         self.calls.append(dict(fn=fn, args=args, desc=dsel, family="conv%dx%d" % (k, k), flops=flops, bytes=nbytes,
                                label="%s %dx%d s%d %d->%d @%dx%d" % (label, k, k, stride, cin, cout, H, W)))
+
+    def _tune_ws(self):
+        """(address, bytes) of a split-K workspace for timing implicit-GEMM candidates (arrival counters in its tail start at zero)."""
+        ws = getattr(self, "_tune_workspace", None)
+        if ws is None:
+            ws = self._tune_workspace = torch.empty(K.WORKSPACE_BYTES, dtype=torch.uint8, device=self.device)
+            ws[-K.WS_COUNTER_BYTES:].zero_()
+        return (ctypes.c_void_p(ws.data_ptr()), K.WORKSPACE_BYTES)
 
     # ---- 3a. a zoomed-conv cell: one fused launch, or (when that measures slower) its separate launches -----------------
     def _tmp_sym(self, shape):
@@ -495,17 +539,25 @@ class InferenceEngine:
             self.calls.append(self._resize_call(t2, out, True))
         chain = self.calls[first:]
         del self.calls[first:]
+        variants = [[fused], chain]
+        if down and self.fold_resizes not in ("0", "off"):
+            # third form: the separate launches with the 1/2 down-sample folded into the first conv's halo staging
+            self._add_conv(x, t1, A["weight"], sc1, sh1, 3, 1, 1, True, cmid, cin, vres=(d.h, d.w, False), vres_halo=True)
+            variants.append(self.calls[first:] + chain[2:])
+            del self.calls[first:]
         # prior from isolated (cache-warm) timings; _tune_cells() then decides on whole-frame time, where the filter banks and
         # the input are cold as they are in production
         if self._plan_in is not None:
-            t_fused = t_chain = 0.0
-            keep_fused = self._plan_in["cells"][len(self.cell_log)] == 0
+            times = [0.0] * len(variants)
+            choice = int(self._plan_in["cells"][len(self.cell_log)])
         else:
-            t_fused, t_chain = self._time_calls([fused]), self._time_calls(chain)
-            keep_fused = t_fused <= t_chain
-        self.cell_log.append([fused["label"], "fused" if keep_fused else "split", round(t_fused * 1e3, 2), round(t_chain * 1e3, 2)])
-        self.calls += [fused] if keep_fused else chain
-        return dict(variants=[[fused], chain], choice=0 if keep_fused else 1, log=self.cell_log[-1])
+            times = [self._time_calls(v) for v in variants]
+            choice = min(range(len(variants)), key=lambda i: (times[i], i))
+        self.cell_log.append([fused["label"], self._VARIANT_NAMES[choice]] + [round(t * 1e3, 2) for t in times])
+        self.calls += variants[choice]
+        return dict(variants=variants, choice=choice, log=self.cell_log[-1])
+
+    _VARIANT_NAMES = ("fused", "split", "split+fold")
 
     def _time_call(self, fn, args, reps=20):
         """Device time (ms) of one launch, replayed back-to-back from a small hipGraph (same method as profile())."""
@@ -566,6 +618,8 @@ class InferenceEngine:
                 scale, shift = self._fold(op["bn"], op["bias"], op["cout"])
                 self._add_conv(op["x"], out, op["weight"], scale, shift, op["k"], op["stride"], op["pad"], op["relu"], op["cout"],
                                op["cin"], vres=op.get("vres"))
+                if op.get("fold") is not None:
+                    alt, in_syms = self._add_fold(op, out, scale, shift, first_call)
             elif kind == "zoom":
                 alt = self._add_zoom(op, out)
             elif kind == "fr":
@@ -613,6 +667,34 @@ class InferenceEngine:
             self.groups.append(group)
         self._flatten()
 
+    def _add_fold(self, op, out, scale, shift, first_call):
+        """The conv just lowered (self.calls[first_call:]) reads a resample that nothing else reads: the alternative is ONE halo launch
+        that interpolates while it stages.  Both forms become variants of this group (the resample's own group goes away); the prior
+        is their isolated time, `_tune_cells` decides in the frame."""
+        rop = op["fold"]
+        ri = next(i for i, g in enumerate(self.groups) if g["out"] is rop["out"])
+        chain = self.groups[ri]["variants"][0] + self.calls[first_call:]
+        del self.groups[ri]
+        del self.calls[first_call:]
+        H, W = rop["out"].shape[2], rop["out"].shape[3]
+        self._add_conv(rop["x"], out, op["weight"], scale, shift, 3, 1, 1, op["relu"], op["cout"], op["cin"],
+                       vres=(H, W, bool(rop["relu"])), vres_halo=True)
+        fused = self.calls[first_call:]
+        del self.calls[first_call:]
+        if self._plan_in is not None:
+            t_fused = t_chain = 0.0
+            keep_fused = self._plan_in["folds"][len(self.fold_log)] == 0
+        elif self.fold_resizes == "auto":
+            t_fused, t_chain = self._time_calls(fused), self._time_calls(chain)
+            keep_fused = t_fused <= t_chain
+        else:
+            t_fused = t_chain = 0.0
+            keep_fused = True
+        self.fold_log.append([fused[0]["label"], "fused" if keep_fused else "split", round(t_fused * 1e3, 2), round(t_chain * 1e3, 2)])
+        self.calls += fused if keep_fused else chain
+        variants = [fused, chain] if (self.fold_resizes == "auto" or self._plan_in is not None) else [fused]
+        return dict(variants=variants, choice=0 if keep_fused else 1, log=self.fold_log[-1]), [rop["x"]]
+
     def _flatten(self):
         """The launch list of the current variant choices, with dependencies, stream lanes and totals."""
         self.calls = []
@@ -620,7 +702,7 @@ class InferenceEngine:
         for g in self.groups:
             deps = sorted({d for s_ in g["in_syms"] for d in self._ready(s_)})
             first = len(self.calls)
-            chain = g["kind"] == "zoom" and len(g["variants"][g["choice"]]) > 1     # un-fused cell: a dependent chain of launches
+            chain = g["kind"] in ("zoom", "conv") and len(g["variants"][g["choice"]]) > 1     # un-fused cell / un-folded resample: a dependent chain of launches
             for k, c in enumerate(g["variants"][g["choice"]]):
                 c = dict(c)
                 c["deps"] = [first + k - 1] if (chain and k > 0) else deps
@@ -635,7 +717,7 @@ class InferenceEngine:
         self.total_bytes = sum(c["bytes"] for c in self.calls)
 
     def _tune_cells(self):
-        """Fused or separate launches, per cell, decided on the time of the WHOLE frame (single-stream hipGraph): timed alone,
+        """Fused or separate launches, per cell (and, per resample in front of a halo 3x3 conv, folded or materialised), decided on the time of the WHOLE frame (single-stream hipGraph): timed alone,
         back to back, a launch finds its filter bank and input in L2, which flatters the fused kernel (it waits on memory in
         several dependent phases).  Greedy: flip one cell at a time, keep the flip if the frame gets faster."""
         cells = [g for g in self.groups if len(g["variants"]) > 1]
@@ -647,14 +729,17 @@ class InferenceEngine:
             return self._time_graph(self._capture_once(1), reps=30)
         best = frame_ms()
         for g in cells:
-            g["choice"] ^= 1
-            t = frame_ms()
-            if t < best * 0.997:
-                best = t
-            else:
-                g["choice"] ^= 1
-            g["log"][1] = "fused" if g["choice"] == 0 else "split"
-            g["log"].append(round(t, 4))
+            keep = g["choice"]
+            for alt in range(len(g["variants"])):
+                if alt == keep:
+                    continue
+                g["choice"] = alt
+                t = frame_ms()
+                if t < best * 0.997:
+                    best, keep = t, alt
+                g["log"].append((alt, round(t, 4)))
+            g["choice"] = keep
+            g["log"][1] = self._VARIANT_NAMES[keep]
         self._flatten()
 
 

@@ -258,18 +258,30 @@ def pack_weight_frag(w, dtype, cout=None, cin=None):
     return out
 
 
-def conv3x3_halo(x, w_frag, cout, scale=None, shift=None, relu=False, out=None, stats=None, stride=1, tile=0):
+def conv3x3_halo(x, w_frag, cout, scale=None, shift=None, relu=False, out=None, stats=None, stride=1, tile=0, ksplit=None, vres=None):
     """3x3 / pad 1 conv at stride 1 or 2 through the halo-tiled kernel (same epilogue contract as conv2d); tile = forced
-    output-channel tile (32 / 64 / 128, 0: heuristic)."""
+    output-channel tile (32 / 64 / 128, 0: heuristic); ksplit = True / 16 / False forces the K-split form with 32- / 16-channel tiles / forbids it (None: the
+    library's rule, fs_conv3x3_halo_plan); vres = (H, W, relu): the convolution reads x bilinearly resampled to H x W
+    (align_corners=True, optional ReLU after the interpolation) while it stages it, stride 1 only."""
     x_cs = require_nhwc(x, "x")
     N, Cin, H, W = x.shape
     flags = (FS_CONV_RELU if relu else 0) | {0: 0, 32: 0x1000, 64: 0x2000, 128: 0x3000}[tile]
-    d = conv_desc(x.shape, x_cs, cout, 3, 3, stride, 1, 0, x.dtype, flags)
+    flags |= 0 if ksplit is None else (_lib.FS_CONV_KSPLIT16 if ksplit == 16 else _lib.FS_CONV_KSPLIT if ksplit else _lib.FS_CONV_NO_KSPLIT)
+    d = conv_desc((N, Cin, vres[0], vres[1]) if vres else x.shape, x_cs, cout, 3, 3, stride, 1, 0, x.dtype, flags)
+    if vres:
+        d.vr_H, d.vr_W, d.vr_relu = H, W, int(bool(vres[2]))
     if out is None:
         out = empty_nhwc(N, cout, d.Ho, d.Wo, x.dtype, x.device)
     d.y_cs = channel_stride(out)
     call("fs_conv3x3_s1_fwd", _stream(), ctypes.byref(d), _p(x), _p(w_frag), _p(scale), _p(shift), _p(out), _p(stats))
     return out
+
+
+def conv3x3_halo_plan(d, has_stats=False):
+    """(tile, ksplit, workgroups) of the launch fs_conv3x3_s1_fwd makes for descriptor `d` (host only, no device needed)."""
+    tile, ks, wg = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+    call("fs_conv3x3_halo_plan", ctypes.byref(d), int(bool(has_stats)), ctypes.byref(tile), ctypes.byref(ks), ctypes.byref(wg))
+    return tile.value, ks.value, wg.value
 
 
 def zoom_desc(x_shape, x_cs, cmid, cout, down, up, y_cs, dtype):

@@ -42,6 +42,11 @@ typedef enum { FS_F32 = 0, FS_BF16 = 1 } fs_dtype;
 #define FS_CONV_TILE_64     0x2000
 #define FS_CONV_TILE_128    0x3000
 #define FS_CONV_TILE_MASK   0x3000
+/* fs_conv3x3_s1_fwd only (ABI 215): force / forbid the K-split form (one 2 x 16 pixel x 32 channel tile per block, the four waves
+ * share the input-channel chunks; stride 1, stats == NULL).  Neither: fs_conv3x3_halo_plan's rule decides. */
+#define FS_CONV_KSPLIT      0x4000
+#define FS_CONV_NO_KSPLIT   0x8000
+#define FS_CONV_KSPLIT16    0x14000 /* FS_CONV_KSPLIT with 16-channel tiles (twice the blocks; the rule takes it below 128 blocks) */
 
 typedef struct fs_conv_desc {
     int N, H, W, Cin;       /* input  (N,H,W,Cin)                                        */
@@ -54,7 +59,7 @@ typedef struct fs_conv_desc {
     int w_os, w_ts;         /* filter strides in elements: row (per output channel) and tap.  0,0 = the dense
                                [Cout][R][S][Cin] pack; otherwise the filter is the leading [:Cout][..][:Cin] block of
                                a wider resident pack (USConv2d slices read in place, slimmable_ops.py:42)         */
-    int vr_H, vr_W;         /* virtual resize (fs_conv2d_fwd[_ws] only): when > 0, x is a (N, vr_H, vr_W, Cin) map and the
+    int vr_H, vr_W;         /* virtual resize (fs_conv2d_fwd[_ws], and fs_conv3x3_s1_fwd at stride 1): when > 0, x is a (N, vr_H, vr_W, Cin) map and the
                                convolution reads its bilinear (align_corners=True) resampling to (H, W), with ReLU after the
                                interpolation if vr_relu - the F.interpolate of the zoomed convs (operations.py:271,275,437,444)
                                folded into the gather instead of materialised by fs_bilinear_fwd                 */
@@ -88,7 +93,7 @@ typedef struct fs_resize_desc {
 const char* fs_last_error(void);
 /* ABI revision of this header; fs_version() returns the one the library was built from.  Bindings check both this and
  * fs_struct_size() when they load the library (fasterseg_amd/_lib.py) - a stale .so must not be used silently. */
-#define FS_ABI_VERSION 214
+#define FS_ABI_VERSION 215
 int fs_version(void);
 /* Bit-reproducible mode (default off; FS_DETERMINISTIC=1 in the environment turns it on at load): every cross-block reduction that
  * otherwise uses float atomics - the pixel slabs of fs_conv2d_wgrad_ws, BatchNorm statistics and parameter gradients of maps above
@@ -166,6 +171,12 @@ fs_status fs_pack_weight_frag(void* stream, const float* w_oihw, long long o_str
                               int dtype, void* w_frag);
 fs_status fs_conv3x3_s1_fwd(void* stream, const fs_conv_desc* d, const void* x, const void* w_frag, const float* scale,
                             const float* shift, void* y, float* stats);
+/* The launch form fs_conv3x3_s1_fwd takes for this descriptor (host only, no device needed; ABI 215): output-channel tile of the block
+ * (32 / 64 / 128; 16 or 32 in the K-split form), ksplit = 1 when the K-split form runs (maps so small that the plain form would launch fewer than half of the
+ * 256 CUs, at least two channel chunks, stride 1, has_stats == 0: a call with BN statistics never selects it), and the number of
+ * workgroups launched.  FS_CONV_TILE_* / FS_CONV_KSPLIT / FS_CONV_NO_KSPLIT in d->flags pin the choice; FS_CONV_KSPLIT with
+ * has_stats or stride 2 is FS_ERR_UNSUPPORTED, here and in fs_conv3x3_s1_fwd.  Any output pointer may be NULL. */
+fs_status fs_conv3x3_halo_plan(const fs_conv_desc* d, int has_stats, int* tile, int* ksplit, long long* workgroups);
 
 /* One launch for a whole zoomed-conv cell in inference form (zoom_cell.hip):
  *   x (N,H,W,Cin) -[bilinear 1/2 if down]-> (h,w) -conv3x3 * scale1 + shift1, ReLU-> Cmid -conv3x3 * scale2 + shift2-> Cout

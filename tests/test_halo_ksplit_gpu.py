@@ -1,0 +1,182 @@
+"""The K-split form of the LDS-halo 3x3 kernel and its resample-at-staging (conv3x3_halo.hip) on a real MI355X.
+
+Reference = F.conv2d (and F.interpolate(align_corners=True) in front of it) in fp32 on the CPU, compared through the `check` helper
+and tolerances of tests/test_kernels_gpu.py::test_conv3x3_halo.  Every case pins the form with FS_CONV_KSPLIT / FS_CONV_KSPLIT16 (32- / 16-channel tiles): chunk
+counts 1, 2, 3, 4, 6, 8 (fewer chunks than waves, uneven shares), a channel tail, ragged maps, Cout not a multiple of 32, output into
+a channel slice, ReLU on / off, N = 2, bit-identical repeats.
+
+BN statistics: the K-split form has no statistics epilogue.  A call with `stats` never selects it (the plain form runs and the sums
+are right) and forcing it together with `stats` is refused with FS_ERR_UNSUPPORTED.
+
+fused == materialised: the staged sample and fs_bilinear_fwd evaluate the same fp32 expression; the compiler may contract it into
+fused multiply-adds differently in the two kernels, so a staged value can differ from the materialised one by one rounding of the
+storage type: |dv| <= eps * max|v| with eps = 2^-8 (bf16) / 2^-23 (fp32).  Through the convolution that is at most
+eps * max|v| * max_co sum|w|, plus one storage rounding of the output (eps * max|y|): the bound asserted below."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from test_kernels_gpu import check, q, rnd
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = [torch.float32, torch.bfloat16]
+
+
+def K():
+    from fasterseg_amd import kernels
+    return kernels
+
+
+def chunk_channels(dtype):
+    return 32 if dtype == torch.bfloat16 else 16
+
+
+FORMS = [True, 16]                                      # FS_CONV_KSPLIT (32-channel tiles), FS_CONV_KSPLIT16
+FORM_IDS = ["ks32", "ks16"]
+
+
+def run_case(dtype, N, Cin, H, W, Cout, relu=True, seed=0, form=True):
+    k = K()
+    x = q(rnd(N, Cin, H, W, seed=seed + 1), dtype)
+    w = q(rnd(Cout, Cin, 3, 3, seed=seed + 2, scale=(2.0 / (Cin * 9)) ** 0.5), dtype)
+    scale, shift = rnd(Cout, seed=seed + 3).abs() + 0.5, rnd(Cout, seed=seed + 4)
+    ref = F.conv2d(x, w, None, 1, 1) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+    if relu:
+        ref = F.relu(ref)
+    xd = k.to_nhwc(x.cuda(), dtype)
+    wf = k.pack_weight_frag(w.cuda(), dtype)
+    y = k.conv3x3_halo(xd, wf, Cout, scale.cuda(), shift.cuda(), relu=relu, ksplit=form)
+    check(y, ref, dtype, "K-split halo %dx%dx%dx%d->%d" % (N, Cin, H, W, Cout))
+    y2 = k.conv3x3_halo(xd, wf, Cout, scale.cuda(), shift.cuda(), relu=relu, ksplit=form)
+    assert torch.equal(y, y2), "two runs of the K-split form differ"
+    return xd, wf, x, w
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
+@pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
+@pytest.mark.parametrize("chunks", [1, 2, 3, 4, 6, 8])
+def test_ksplit_chunk_counts(chunks, form, dtype):
+    """1-3 chunks: waves without work; 6: shares of 2, 2, 1, 1; 8: two chunks per wave (the double-buffered patch)."""
+    run_case(dtype, 1, chunks * chunk_channels(dtype), 16, 32, 64, form=form)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
+@pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
+@pytest.mark.parametrize("relu", [False, True], ids=["linear", "relu"])
+def test_ksplit_channel_tail_ragged_map_batch(dtype, relu, form):
+    """Cin ends inside the last chunk (and inside a wave's only chunk), H and W are no multiples of 2 / 16, N = 2."""
+    ck = chunk_channels(dtype)
+    vec = 8 if dtype == torch.bfloat16 else 4
+    run_case(dtype, 2, 5 * ck + vec, 7, 21, 64, relu=relu, seed=10, form=form)
+    run_case(dtype, 2, 2 * ck - vec, 5, 35, 32, relu=relu, seed=20, form=form)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
+@pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
+@pytest.mark.parametrize("cout", [19, 40, 96, 144])
+def test_ksplit_cout_tails(cout, form, dtype):
+    """Cout not a multiple of 32: the last n-tile is partly empty (element stores instead of the LDS transpose)."""
+    run_case(dtype, 1, 4 * chunk_channels(dtype), 9, 18, cout, seed=30, form=form)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
+@pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
+def test_ksplit_into_channel_slice(form, dtype):
+    k = K()
+    N, Cin, H, W, Cout = 2, 6 * chunk_channels(dtype), 16, 32, 64
+    x = q(rnd(N, Cin, H, W, seed=41), dtype)
+    w = q(rnd(Cout, Cin, 3, 3, seed=42, scale=(2.0 / (Cin * 9)) ** 0.5), dtype)
+    raw = F.conv2d(x, w, None, 1, 1)
+    wide = k.empty_nhwc(N, Cout + 64, H, W, dtype, "cuda", zero=True)
+    k.conv3x3_halo(k.to_nhwc(x.cuda(), dtype), k.pack_weight_frag(w.cuda(), dtype), Cout, out=wide[:, 32:32 + Cout], ksplit=form)
+    check(wide[:, 32:32 + Cout], raw, dtype, "K-split halo into slice")
+    assert float(wide[:, :32].abs().max()) == 0.0 and float(wide[:, 32 + Cout:].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
+def test_ksplit_matches_plain_form(dtype):
+    """Same layer through the plain form: both within tolerance of the reference; they differ only in the order of the fp32 sums."""
+    k = K()
+    xd, wf, x, w = run_case(dtype, 1, 8 * chunk_channels(dtype), 16, 32, 128, relu=False, seed=50)
+    ref = F.conv2d(x, w, None, 1, 1)
+    scale, shift = rnd(128, seed=53).abs() + 0.5, rnd(128, seed=54)
+    ref = ref * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+    plain = k.conv3x3_halo(xd, wf, 128, scale.cuda(), shift.cuda(), ksplit=False)
+    check(plain, ref, dtype, "plain halo")
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
+def test_stats_calls_never_take_the_ksplit_form(dtype):
+    """Training epilogue: the library's rule keeps the plain form (right sums on a map where inference would split), the plan export
+    says so, and forcing the split form with statistics is an error, not a silent drop of the sums."""
+    from fasterseg_amd._lib import FasterSegHipError
+    k = K()
+    N, Cin, H, W, Cout = 1, 4 * chunk_channels(dtype), 16, 32, 64
+    x = q(rnd(N, Cin, H, W, seed=61), dtype)
+    w = q(rnd(Cout, Cin, 3, 3, seed=62, scale=(2.0 / (Cin * 9)) ** 0.5), dtype)
+    raw = F.conv2d(x, w, None, 1, 1)
+    xd, wf = k.to_nhwc(x.cuda(), dtype), k.pack_weight_frag(w.cuda(), dtype)
+    d = k.conv_desc(x.shape, Cin, Cout, 3, 3, 1, 1, Cout, dtype)
+    assert k.conv3x3_halo_plan(d, has_stats=False)[1] == 1
+    assert k.conv3x3_halo_plan(d, has_stats=True)[1] == 0
+    stats = torch.zeros(2 * Cout, device="cuda")
+    y = k.conv3x3_halo(xd, wf, Cout, stats=stats)
+    check(y, raw, dtype, "halo with stats on a small map")
+    cnt = raw.numel() / Cout
+    assert torch.allclose(stats[:Cout].cpu(), raw.sum((0, 2, 3)), atol=2e-3 * cnt ** 0.5 + 1e-3, rtol=2e-3)
+    assert torch.allclose(stats[Cout:].cpu(), (raw * raw).sum((0, 2, 3)), atol=1e-3, rtol=3e-3)
+    with pytest.raises(FasterSegHipError, match="K-split"):
+        k.conv3x3_halo(xd, wf, Cout, stats=stats, ksplit=True)
+
+
+# ---- resample-at-staging ---------------------------------------------------------------------------------------------------------
+VRES_CASES = [
+    # N, Cin(chunks), source H, W, resampled H, W, Cout
+    (1, 4, 32, 64, 16, 32, 64),          # the student's 1/2 down-sample in front of a 3x3
+    (2, 3, 17, 29, 8, 14, 48),           # odd source, ragged resampled map, Cout tail, N = 2
+    (1, 2, 9, 13, 18, 26, 32),           # x2 up-sample
+    (1, 6, 15, 21, 29, 41, 64),          # up-sample to odd sizes
+]
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
+@pytest.mark.parametrize("ksplit", [True, 16, False], ids=["ks32", "ks16", "plain"])
+@pytest.mark.parametrize("vrelu", [False, True], ids=["lin", "vrelu"])
+@pytest.mark.parametrize("case", VRES_CASES, ids=["%dx%dc-%dx%d-to-%dx%d-%d" % c for c in VRES_CASES])
+def test_resample_at_staging(case, vrelu, ksplit, dtype):
+    """conv(resample(x)) in one launch == F.interpolate(align_corners=True) [-> ReLU] -> F.conv2d on the CPU, and == the materialised
+    path (fs_bilinear_fwd, then the same conv form) to one storage rounding of the staged value (module docstring)."""
+    k = K()
+    N, chunks, Hs, Ws, H, W, Cout = case
+    Cin = chunks * chunk_channels(dtype)
+    x = q(rnd(N, Cin, Hs, Ws, seed=71), dtype)
+    w = q(rnd(Cout, Cin, 3, 3, seed=72, scale=(2.0 / (Cin * 9)) ** 0.5), dtype)
+    scale, shift = rnd(Cout, seed=73).abs() + 0.5, rnd(Cout, seed=74)
+    v = F.interpolate(x, size=(H, W), mode="bilinear", align_corners=True)
+    if vrelu:
+        v = F.relu(v)
+    v = q(v, dtype)                                       # the staged / materialised map is stored in `dtype`
+    ref = F.relu(F.conv2d(v, w, None, 1, 1) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
+    xd, wf = k.to_nhwc(x.cuda(), dtype), k.pack_weight_frag(w.cuda(), dtype)
+    fused = k.conv3x3_halo(xd, wf, Cout, scale.cuda(), shift.cuda(), relu=True, ksplit=ksplit, vres=(H, W, vrelu))
+    assert tuple(fused.shape) == (N, Cout, H, W)
+    check(fused, ref, dtype, "resample-at-staging")
+    again = k.conv3x3_halo(xd, wf, Cout, scale.cuda(), shift.cuda(), relu=True, ksplit=ksplit, vres=(H, W, vrelu))
+    assert torch.equal(fused, again)
+    mat = k.bilinear(xd, (H, W), relu=vrelu)
+    sep = k.conv3x3_halo(mat, wf, Cout, scale.cuda(), shift.cuda(), relu=True, ksplit=ksplit)
+    eps = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -23
+    bound = eps * (float(v.abs().max()) * float((w.abs().sum((1, 2, 3)) * scale.abs()).max()) + float(ref.abs().max()))
+    diff = float((fused.float() - sep.float()).abs().max())
+    print("fused vs materialised: max |diff| %.3e, bound %.3e" % (diff, bound))
+    assert diff <= bound, (diff, bound)
+
+
+def test_resample_at_staging_rejects_stride_2():
+    from fasterseg_amd._lib import FasterSegHipError
+    k = K()
+    x = k.to_nhwc(rnd(1, 32, 16, 16, seed=81).cuda(), torch.bfloat16)
+    wf = k.pack_weight_frag(rnd(32, 32, 3, 3, seed=82).cuda(), torch.bfloat16)
+    with pytest.raises(FasterSegHipError, match="stride 1"):
+        k.conv3x3_halo(x, wf, 32, stride=2, vres=(8, 8, False))
