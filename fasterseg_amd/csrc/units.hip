@@ -20,6 +20,8 @@ static const long long BN_COL_MAX_PIXELS = 512;
 // the L2 serialises at ~20 ns each (tools/census_shapes.py c4, r04: a 32->32 conv on 12 x 64 x 128 pixels took 80 us with them, 12 us
 // without).  A separate pass over z (chan_reduce_kernel: >= 256 pixels per block, one atomic per channel per block) costs a launch
 // plus one read of the map, so the epilogue only keeps the statistics of maps where that is more than the atomics.
+// (tests/_grouped_cases.py restates this rule, BN_COL_MAX_PIXELS and the 32-row group rule of unit_fwd_group's mode[] to predict the
+// launches of its unit table - stats_in_epilogue() and UnitProblem.mode there: retune them together, and keep units on both sides)
 static bool stats_in_epilogue(long long M, int C, int dtype) {
     const double epilogue_us = (double)M / 32 * 0.02;
     const double pass_us = 8.0 + (double)M * C * (dtype == FS_F32 ? 4 : 2) / 3.0e6;

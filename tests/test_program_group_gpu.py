@@ -63,12 +63,23 @@ def test_lockstep_group_equals_single_programs(kinds, sizes, groups, phase, dtyp
             assert names == ({"_MixedOpProgramGroupBackward"} if group else {"_MixedOpProgramBackward"}), names
             torch.autograd.backward(outs, dys0)
             rec = {"out": torch.cat([o.detach().float().reshape(-1) for o in outs]), "dx": torch.cat([x.grad.float().reshape(-1) for x in xs])}
+            # ... and every tensor on its own: program by program, parameter by parameter
+            parts = {}
+            for k, (o, x) in enumerate(zip(outs, xs)):
+                parts["out[%d]" % k] = o.detach().float().reshape(-1).clone()
+                parts["dx[%d]" % k] = x.grad.float().reshape(-1).clone()
             if phase == "a":
                 rec["dcoef"] = torch.cat([c.grad for c in coefs])
+                for k, c in enumerate(coefs):
+                    parts["dcoef[%d]" % k] = c.grad.clone()
             else:
                 sync.sync()
                 rec["flat"] = sync.flat.clone()
                 rec["touched"] = list(sync._touched)
+                names_of = {id(p): name for name, p in ops.named_parameters()}
+                for p, off in zip(sync.params, sync.offsets):          # each parameter's slice of the flat gradient, by the sync's offsets
+                    parts["flat " + names_of[id(p)]] = rec["flat"][off:off + p.numel()]
+            rec["parts"] = parts
             rec["running"] = torch.cat([b.float().reshape(-1) for n, b in ops.named_buffers()])
             got.append(rec)
     finally:
@@ -81,5 +92,18 @@ def test_lockstep_group_equals_single_programs(kinds, sizes, groups, phase, dtyp
         if k == "touched":
             assert ref[k] == new[k]
             continue
+        if k == "parts":
+            continue
         rel = float((ref[k] - new[k]).norm() / (ref[k].norm() + 1e-12))
+        assert rel < tol, (k, rel)
+    # the same bar per program and per tensor (out, dx, dcoef, each parameter's slice of the flat gradient): a small map cannot hide behind
+    # a large one in the concatenated norm
+    assert ref["parts"].keys() == new["parts"].keys()
+    assert any(k.startswith("dcoef[" if phase == "a" else "flat ") for k in ref["parts"])
+    for k, a in ref["parts"].items():
+        b = new["parts"][k]
+        assert a.shape == b.shape, k
+        if float(a.norm()) == 0.0 and float(b.norm()) == 0.0:          # a slice neither path touched
+            continue
+        rel = float((a - b).norm() / (a.norm() + 1e-12))
         assert rel < tol, (k, rel)
