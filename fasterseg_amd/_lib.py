@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfasterseg_hip.so")
 
-EXPECTED_ABI = 215          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
+EXPECTED_ABI = 216          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
 FS_F32, FS_BF16 = 0, 1
 FS_CONV_RELU, FS_CONV_TRANSPOSED, FS_CONV_ACCUM, FS_CONV_RELU_TAIL = 1, 2, 4, 8
 FS_CONV_KSPLIT, FS_CONV_NO_KSPLIT, FS_CONV_KSPLIT16 = 0x4000, 0x8000, 0x14000   # fs_conv3x3_s1_fwd: force / forbid the K-split form (16: 16-channel tiles)
@@ -57,6 +57,14 @@ class HeadsDesc(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("K", "N", "h", "w", "C", "H", "W", "dtype")] + [("cs", c_int * FS_MAX_HEADS)]
 
 
+FS_RENDER_MAX_PANELS = 4
+
+
+class RenderDesc(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("H", "W", "panels", "image_panel", "gap", "dst_pitch", "n_colors", "background", "write_ids")] + [
+        ("show255", c_int * FS_RENDER_MAX_PANELS), ("alpha", c_float * FS_RENDER_MAX_PANELS), ("beta", c_float * FS_RENDER_MAX_PANELS)]
+
+
 class CensusEntry(ctypes.Structure):
     _fields_ = [("family", c_int), ("desc", ConvDesc), ("count", c_ll), ("ms", ctypes.c_double)]
 
@@ -96,6 +104,7 @@ SIGNATURES = {
     "fs_eval_rescale_accumulate": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp],
     "fs_train_batch": [c_vp, ctypes.POINTER(TrainBatchDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "fs_resize_u8": [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int],
+    "fs_render_prediction": [c_vp, ctypes.POINTER(RenderDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "fs_bilinear_bwd": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp, c_vp],
     "fs_bilinear_bwd_nchw": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp, c_vp],
     "fs_bn_finalize": [c_vp, c_int, c_ll, c_vp, c_vp, c_vp, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -205,7 +214,7 @@ def lib():
             raise ImportError("libfasterseg_hip.so has ABI %d, these bindings expect %d: rebuild with `python -m fasterseg_amd.build "
                               "--force`" % (got, EXPECTED_ABI))
         for which, struct in enumerate((ConvDesc, ResizeDesc, ZoomDesc, SgdTensor, LogitsDesc, EvalWindowDesc,
-                                           TrainSample, TrainBatchDesc, HeadsDesc)):
+                                           TrainSample, TrainBatchDesc, HeadsDesc, RenderDesc)):
             if handle.fs_struct_size(which) != ctypes.sizeof(struct):
                 raise ImportError("libfasterseg_hip.so: sizeof(%s) is %d in the library, %d in the bindings - stale build" % (
                     struct.__name__, handle.fs_struct_size(which), ctypes.sizeof(struct)))

@@ -42,6 +42,7 @@ extern "C" int fs_struct_size(int which) {
         case 6: return (int)sizeof(fs_train_sample);
         case 7: return (int)sizeof(fs_train_batch_desc);
         case 8: return (int)sizeof(fs_heads_desc);
+        case 9: return (int)sizeof(fs_render_desc);
         default: return -1;
     }
 }

@@ -12,6 +12,8 @@ the uint8 image (cv2's fixed-point bilinear resize, padding, normalisation, the 
 fs_eval_score_accumulate adds exp(l + unflip(l_flip)) of the x8 up-sampled logits into a per-scale canvas, and
 fs_eval_rescale_accumulate resizes each scale's canvas back to the image (cv2 INTER_LINEAR on float) into the total, taking the
 arg-max on the last scale.  The host only plans (fasterseg_amd.eval_plan) and issues launches."""
+import os
+
 import numpy as np
 import torch
 
@@ -36,7 +38,8 @@ class _ImageState:
 
 class SegEvaluator:
     def __init__(self, network, class_num, image_mean, image_std, image_shape=(1024, 2048), dtype=torch.bfloat16, device="cuda",
-                 multi_scales=(1,), is_flip=False, crop_size=None, stride_rate=5 / 6):
+                 multi_scales=(1,), is_flip=False, crop_size=None, stride_rate=5 / 6, save_path=None, show_image=False,
+                 show_prediction=False, labels=None):
         self.class_num = class_num
         self.device = torch.device(device)
         self.image_mean = torch.tensor(np.asarray(image_mean, dtype=np.float32), device=self.device).view(1, 3, 1, 1)
@@ -61,6 +64,12 @@ class SegEvaluator:
         self.cs = K.round_up(class_num, 4)          # fp32 canvas / total channel stride (19 -> 20)
         self._lowres = {}                           # input shape -> "lowres" engine
         self._states = {}                           # (H, W) -> _ImageState
+        # train/eval.py:30-51, off by default: files per frame (data['fn']) through a tester.PredictionWriter created on first use
+        self.save_path = save_path
+        self.show_image = bool(show_image)
+        self.show_prediction = bool(show_prediction)
+        self.labels = labels                        # visualize.LabelSpec: the colours of the pictures
+        self._writer = None
 
     def process_image(self, img):
         """HWC uint8 (numpy or tensor, RGB like the reference after its BGR->RGB flip) -> normalised (1, 3, H, W) fp32 on the
@@ -194,7 +203,41 @@ class SegEvaluator:
             pred = self.sliding_eval(data['data'], self.crop_size, self.stride_rate)
         label = torch.as_tensor(data['label']).to(self.device)
         self.acc.add(pred, label.contiguous())
+        if self.save_path is not None or self.show_image or self.show_prediction:
+            self._save(data, pred, label)
         return pred
+
+    def _save(self, data, pred, label):
+        """train/eval.py:30-51: `<fn>.png` under save_path (the working directory without one) - with show_image the image |
+        prediction | ground-truth strip, with show_prediction the painted image, else the raw class map.  The reference writes the
+        picture after the map, so where both land in one directory the picture is what the file holds; the same here."""
+        from . import tester, visualize as V
+        if self._writer is None:
+            self._writer = tester.PredictionWriter(device=self.device)
+        folder = self.save_path if self.save_path is not None else os.getcwd()
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, data['fn'] + ".png")
+        H, W = int(pred.shape[0]), int(pred.shape[1])
+        if not (self.show_image or self.show_prediction):
+            self._writer.submit([(path, (H, W))], lambda views: views[0].copy_(pred))
+            return
+        if self.labels is None:
+            raise ValueError("show_image / show_prediction need labels (a visualize.LabelSpec)")
+        img = torch.as_tensor(data['data']).to(self.device).contiguous()
+        if self.show_image:
+            gt = label if label.dtype == torch.uint8 else label.to(torch.uint8)       # 255 and -1 both: 255
+            Wt = 3 * W + 2 * V.PIVOT
+            self._writer.submit([(path, (H, Wt, 3))], lambda views: V.compose(self.labels, self.labels.background, img, [pred, gt],
+                                                                              [False, True], [0.55, 0.55], image_panel=True, out=views[0]))
+        else:
+            self._writer.submit([(path, (H, W, 3))], lambda views: V.compose(self.labels, self.labels.background, img, [pred], [False], [1],
+                                                                             out=views[0]))
+
+    def finish_writing(self):
+        """Block until every file queued by func_per_iteration is on disk (re-raises a writer thread's exception)."""
+        if self._writer is not None:
+            writer, self._writer = self._writer, None
+            writer.close()
 
     def compute_metric(self):
         hist, labeled, correct = self.acc.result()

@@ -676,6 +676,49 @@ def resize_u8(src, out, ytab, xtab, nearest):
     return out
 
 
+def render_prediction(image, maps, palette, composite=None, col=0, image_panel=False, gap=15, background=-1, show255=(), weights=(),
+                      lut=None, ids=None):
+    """fs_render_prediction: image (H, W, 3) uint8 and up to 4 class maps (H, W) uint8 -> the panels of one launch written into
+    `composite` ((H, Wc, 3) uint8, strides (pitch, 3, 1)) from pixel column `col` on: the untouched image first with image_panel, then
+    one overlay per map (set_img_color with show255[i] and weight_foreground weights[i]), `gap` black columns between the panels;
+    with `ids` ((H, W) uint8) also ids = lut[maps[0]] (lut: 256 uint8).  palette: (n, 3) uint8 RGB, n <= 256.  Without weights
+    (no overlay panel) `maps` holds the one map of the ids; without any panel composite and image may be None.  Returns the pixel
+    columns written (0 without a composite)."""
+    maps = list(maps)
+    panels = len(weights)
+    assert len(show255) == panels <= _lib.FS_RENDER_MAX_PANELS, "one show255 and one weight per overlay panel, 4 at the most"
+    assert len(maps) == panels or (panels == 0 and len(maps) == 1 and ids is not None), "one class map per overlay panel (or the one of the ids)"
+    assert composite is not None or (panels == 0 and not image_panel), "panels need a composite"
+    H, W = (int(v) for v in maps[0].shape) if maps else (int(v) for v in image.shape[:2])
+    for m in maps:
+        assert m.dtype == torch.uint8 and m.is_cuda and m.is_contiguous() and tuple(m.shape) == (H, W), "class maps: (H, W) uint8, contiguous"
+    P = panels + int(bool(image_panel))
+    span = W * P + int(gap) * (P - 1) if P else 0
+    d = _lib.RenderDesc(H, W, panels, int(bool(image_panel)), int(gap), 0, 0, int(background), int(ids is not None))
+    dst = None
+    if P:
+        assert image.dtype == torch.uint8 and image.is_cuda and image.is_contiguous() and tuple(image.shape) == (H, W, 3), "image: (H, W, 3) uint8"
+        assert composite.dtype == torch.uint8 and composite.is_cuda and composite.dim() == 3 and composite.shape[0] == H and \
+            composite.shape[2] == 3 and composite.stride(1) == 3 and composite.stride(2) == 1, "composite: (H, Wc, 3) uint8 rows"
+        assert 0 <= col and col + span <= composite.shape[1], "the panels do not fit the composite"
+        d.dst_pitch = int(composite.stride(0)) if H > 1 else max(int(composite.stride(0)), 3 * span)
+        dst = ctypes.c_void_p(composite.data_ptr() + 3 * int(col))
+    if panels:
+        assert palette.dtype == torch.uint8 and palette.is_cuda and palette.is_contiguous() and palette.dim() == 2 and palette.shape[1] == 3
+        d.n_colors = int(palette.shape[0])
+        for i in range(panels):
+            d.show255[i] = int(bool(show255[i]))
+            d.alpha[i] = float(weights[i])
+            d.beta[i] = 1.0 - float(weights[i])          # the subtraction in double, as the reference's (1 - weight_foreground)
+    if ids is not None:
+        assert ids.dtype == torch.uint8 and ids.is_cuda and ids.is_contiguous() and tuple(ids.shape) == (H, W)
+        assert lut.dtype == torch.uint8 and lut.is_cuda and lut.is_contiguous() and lut.numel() == 256
+    ptrs = (ctypes.c_void_p * _lib.FS_RENDER_MAX_PANELS)(*[m.data_ptr() for m in maps])
+    call("fs_render_prediction", _stream(), ctypes.byref(d), _p(image) if P else None, ptrs, _p(palette) if panels else None, _p(lut),
+         dst, _p(ids))
+    return span
+
+
 def deterministic_on():
     """Is the library in its bit-reproducible mode (fs_set_deterministic / FS_DETERMINISTIC=1)?"""
     return bool(_lib.lib().fs_get_deterministic())

@@ -1,0 +1,228 @@
+"""Test-set inference to files (drop-in for the reference's train/test.py SegTester + tools/engine/tester.py).
+
+The reference, per frame, copies the score map to the host, maps train ids to label ids in a Python double loop over every
+pixel (test.py:66-68), paints the overlay with np.where passes (visualize.py) and calls cv2.imwrite twice.  Here the class
+map never leaves the device until it is a finished picture: one fs_render_prediction launch writes the label-ID map and the
+overlay into a staging slot, an asynchronous copy brings the bytes to pinned host memory, and worker threads encode the PNGs
+while the next frames run (PredictionWriter)."""
+import os
+import queue
+import threading
+
+import numpy as np
+import torch
+
+from . import kernels as K
+from .evaluator import SegEvaluator
+
+MAX_WORKERS = 16
+
+
+def save_png(path, array, compress_level=1):
+    """(H, W) uint8 -> a single-channel ('L') PNG, (H, W, 3) uint8 -> an RGB PNG."""
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(array)).save(path, format="PNG", compress_level=compress_level)
+
+
+def _layout(shapes):
+    """Byte offsets / pitches of the outputs of one submission inside a slot: every output starts 16 bytes aligned, and so does every
+    row of an (H, W, 3) picture (its pitch is rounded up); an (H, W) map is dense, as fs_render_prediction writes it."""
+    plan, off = [], 0
+    for shape in shapes:
+        row = int(shape[1]) * (3 if len(shape) == 3 else 1)
+        pitch = K.round_up(row, 16) if len(shape) == 3 else row
+        plan.append((off, pitch, row))
+        off = K.round_up(off + pitch * int(shape[0]), 16)
+    return plan, off
+
+
+class _Slot:
+    """One staging slot: a device buffer the kernels render into, a pinned host buffer of the same size the finished bytes are
+    copied to, and the event behind that copy.  With device=None both are one numpy array (host-side producers)."""
+
+    def __init__(self, device):
+        self.device = device
+        self.dev = self.host = self.event = None
+        self.size = 0
+
+    def views(self, shapes):
+        plan, need = _layout(shapes)
+        if need > self.size:
+            if self.device is None:
+                self.dev = self.host = np.empty(need, dtype=np.uint8)
+            else:
+                self.dev = torch.empty(need, dtype=torch.uint8, device=self.device)
+                self.host = torch.empty(need, dtype=torch.uint8, pin_memory=True)
+                self.event = torch.cuda.Event()
+            self.size = need
+        self.need = need
+        host = self.host if self.device is None else self.host.numpy()
+        dev, hst = [], []
+        for shape, (off, pitch, row) in zip(shapes, plan):
+            H = int(shape[0])
+            d = self.dev[off:off + H * pitch].reshape(H, pitch)[:, :row]
+            h = host[off:off + H * pitch].reshape(H, pitch)[:, :row]
+            if len(shape) == 3:
+                d = d.reshape(H, row // 3, 3) if self.device is None else d.unflatten(1, (row // 3, 3))
+                h = h.reshape(H, row // 3, 3)
+            dev.append(d)
+            hst.append(h)
+        return dev, hst
+
+    def publish(self):
+        """Queue the device -> pinned copy of what was rendered behind the kernels of the current stream."""
+        if self.device is not None:
+            self.host[:self.need].copy_(self.dev[:self.need], non_blocking=True)
+            self.event.record()
+
+    def wait(self):
+        if self.event is not None:
+            self.event.synchronize()
+
+
+class PredictionWriter:
+    """PNG files written behind the device.  submit(outputs, render) takes a free slot (blocks while every slot is in flight), lets
+    `render` fill the slot's device views, queues the copy to pinned memory on the current stream and returns; a worker thread
+    waits for the copy, encodes the files (zlib releases the GIL) and only then frees the slot.  close() joins the workers and
+    re-raises the first exception one of them met.  Threads only; `workers` is capped at 16 whatever the host has."""
+
+    def __init__(self, slots=4, workers=4, device="cuda", encode=None, compress_level=1):
+        if slots < 1 or workers < 1:
+            raise ValueError("PredictionWriter: at least one slot and one worker")
+        self.encode = encode if encode is not None else (lambda path, array: save_png(path, array, compress_level))
+        self._free = queue.Queue()
+        for _ in range(slots):
+            self._free.put(_Slot(None if device is None else torch.device(device)))
+        self._jobs = queue.Queue()
+        self._error = None
+        self._lock = threading.Lock()
+        self._threads = [threading.Thread(target=self._work, name="fs-png-%d" % i, daemon=True) for i in range(min(int(workers), MAX_WORKERS))]
+        for t in self._threads:
+            t.start()
+
+    def submit(self, outputs, render):
+        """outputs: [(path, shape)], shape (H, W) or (H, W, 3); render(views) fills the uint8 views (one per output, rows 16 bytes
+        aligned) - device tensors, or numpy arrays for a writer built with device=None."""
+        if not self._threads:
+            raise RuntimeError("PredictionWriter is closed")
+        slot = self._free.get()
+        try:
+            dev, host = slot.views([shape for _, shape in outputs])
+            render(dev)
+            slot.publish()
+        except BaseException:
+            self._free.put(slot)
+            raise
+        self._jobs.put((slot, [(path, h) for (path, _), h in zip(outputs, host)]))
+
+    def _work(self):
+        while True:
+            job = self._jobs.get()
+            if job is None:
+                self._jobs.task_done()
+                return
+            slot, files = job
+            try:
+                slot.wait()
+                for path, array in files:
+                    self.encode(path, array)
+            except BaseException as e:          # kept for close(): a worker must not die with a slot in its hands
+                with self._lock:
+                    if self._error is None:
+                        self._error = e
+            finally:
+                self._free.put(slot)             # the files of this slot are closed: it may be rendered into again
+                self._jobs.task_done()
+
+    def flush(self):
+        """Block until every submitted file is written; re-raise the first worker exception."""
+        self._jobs.join()
+        self._raise()
+
+    def _raise(self):
+        with self._lock:
+            e, self._error = self._error, None
+        if e is not None:
+            raise e
+
+    def close(self):
+        threads, self._threads = self._threads, []
+        for _ in threads:
+            self._jobs.put(None)
+        for t in threads:
+            t.join()
+        self._raise()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class SegTester(SegEvaluator):
+    """train/test.py SegTester: per frame `<fn>.png`, the prediction as a single-channel PNG of label ids, and with show_prediction
+    `<fn>.viz.png`, the image painted by the prediction (RGB), under save_dir.  labels: a visualize.LabelSpec.  evaluator_kwargs go
+    to SegEvaluator (image_shape, dtype, multi_scales, is_flip, crop_size, stride_rate); slots / workers size the writer;
+    write=False renders every frame but writes no file (timing)."""
+
+    def __init__(self, network, class_num, image_mean, image_std, labels, save_dir, show_prediction=False, slots=4, workers=4,
+                 write=True, **evaluator_kwargs):
+        super().__init__(network, class_num, image_mean, image_std, **evaluator_kwargs)
+        self.labels = labels
+        self.save_dir = save_dir
+        self.show_prediction = bool(show_prediction)
+        self.labeled_frames = 0
+        self.writer = None
+        self._scratch = _Slot(self.device)
+        if write:
+            os.makedirs(save_dir, exist_ok=True)
+            self.writer = PredictionWriter(slots=slots, workers=workers, device=self.device)
+
+    def _render(self, img, pred, views):
+        palette, lut = self.labels.tables(self.device)
+        if self.show_prediction:
+            K.render_prediction(img, [pred], palette, views[1], gap=0, background=self.labels.background, show255=[False], weights=[1],
+                                lut=lut, ids=views[0])
+        else:
+            K.render_prediction(None, [pred], None, lut=lut, ids=views[0])
+
+    def func_per_iteration(self, data):
+        """data: {'data': HWC uint8 image, 'label': (H, W) labels or None, 'fn': name}.  Dispatch of test.py:55-58; the files are
+        queued, the class map is returned; frames with a label are accumulated for compute_metric."""
+        if len(self.multi_scales) == 1:
+            pred = self.whole_eval(data['data'])
+        else:
+            pred = self.sliding_eval(data['data'], self.crop_size, self.stride_rate)
+        H, W = int(pred.shape[0]), int(pred.shape[1])
+        img = None
+        outputs = [(os.path.join(self.save_dir, data['fn'] + ".png"), (H, W))]
+        if self.show_prediction:
+            img = torch.as_tensor(data['data']).to(self.device).contiguous()
+            outputs.append((os.path.join(self.save_dir, data['fn'] + ".viz.png"), (H, W, 3)))
+        if self.writer is not None:
+            self.writer.submit(outputs, lambda views: self._render(img, pred, views))
+        else:
+            self._render(img, pred, self._scratch.views([shape for _, shape in outputs])[0])
+        label = data.get('label')
+        if label is not None:
+            self.acc.add(pred, torch.as_tensor(label).to(self.device).contiguous())
+            self.labeled_frames += 1
+        return pred
+
+    def run_online(self, dataset):
+        """Every frame of an iterable of such dicts; returns when the last file is on disk.  The metric (compute_metric) when the
+        frames carried labels, else None."""
+        for data in dataset:
+            self.func_per_iteration(data)
+        if self.writer is not None:
+            self.writer.flush()
+        else:
+            torch.cuda.synchronize(self.device)
+        return self.compute_metric() if self.labeled_frames else None
+
+    def close(self):
+        if self.writer is not None:
+            writer, self.writer = self.writer, None
+            writer.close()

@@ -93,7 +93,7 @@ typedef struct fs_resize_desc {
 const char* fs_last_error(void);
 /* ABI revision of this header; fs_version() returns the one the library was built from.  Bindings check both this and
  * fs_struct_size() when they load the library (fasterseg_amd/_lib.py) - a stale .so must not be used silently. */
-#define FS_ABI_VERSION 215
+#define FS_ABI_VERSION 216
 int fs_version(void);
 /* Bit-reproducible mode (default off; FS_DETERMINISTIC=1 in the environment turns it on at load): every cross-block reduction that
  * otherwise uses float atomics - the pixel slabs of fs_conv2d_wgrad_ws, BatchNorm statistics and parameter gradients of maps above
@@ -110,8 +110,8 @@ int fs_get_deterministic(void);
 void fs_set_fp32_split(int on);
 int fs_get_fp32_split(void);
 int fs_struct_size(int which);   /* 0 fs_conv_desc, 1 fs_resize_desc, 2 fs_zoom_desc, 3 fs_sgd_tensor, 4 fs_logits_desc,
-                                    5 fs_eval_window_desc, 6 fs_train_sample, 7 fs_train_batch_desc, 8 fs_heads_desc;
-                                    -1 otherwise */
+                                    5 fs_eval_window_desc, 6 fs_train_sample, 7 fs_train_batch_desc, 8 fs_heads_desc,
+                                    9 fs_render_desc; -1 otherwise */
 /* test hook: force the tile configuration of fs_conv2d_fwd (0..7; -1 = heuristic).  Not for production use. */
 void fs_debug_force_conv_cfg(int cfg);
 /* number of elements of a packed filter bank for (Cout,R,S,Cin) */
@@ -643,6 +643,35 @@ long long fs_train_batch_args_bytes(int B);
  * int32).  dst must not overlap src. */
 fs_status fs_resize_u8(void* stream, const unsigned char* src, int H, int W, int C, unsigned char* dst, int h, int w, const int* ytab,
                        const int* xtab, int mode);
+/* --- prediction rendering: label-ID maps and colour overlays (ABI 216) ------------------------------------------------ */
+/* What the reference does on the host with a finished class map, per frame: tools/utils/visualize.py:6-41 (set_img_color: every class
+ * but `background` painted in its colour, label 255 painted black with show255, then cv2.addWeighted(painted, w, image, 1 - w, 0);
+ * show_prediction: one such panel; show_img: the image, one panel per prediction and the ground-truth panel side by side, a 15-column
+ * black pivot between them) and train/test.py:66-69 (the trainId -> labelId map, pixel by pixel).  One launch writes the whole composite
+ * and, optionally, the label-ID map.
+ * Composite row: P = image_panel + panels panels of W pixels (RGB bytes), `gap` black pixels between neighbours; panel p starts at byte
+ * 3 * p * (W + gap).  Bytes behind the last panel (the padding of dst_pitch) are not touched.  Per overlay panel i (class map maps[i],
+ * H x W uint8), pixel and channel, with o the image byte and k the class:
+ *   c = palette[3 * k + channel] if k < n_colors and k != background, else o;  c = 0 if show255[i] and k == 255;
+ *   out = saturate_u8(rint_half_even(fmaf((float)c, alpha[i], (float)o * beta[i])))   (fp32, the product rounded before the fused add).
+ * write_ids: ids[y * W + x] = lut[maps[0][y * W + x]].  composite and image may be NULL only when panels == 0 and image_panel == 0 (ids
+ * only); maps is a HOST array of device pointers, entries [0, panels) are read (entry 0 with write_ids).  No alignment is required of
+ * any pointer or of dst_pitch: rows are written with 16-byte stores from the first 16-byte boundary of each panel row on. */
+#define FS_RENDER_MAX_PANELS 4
+typedef struct fs_render_desc {
+    int H, W;               /* size of the image and of every class map                                                        */
+    int panels;             /* 0..4 overlay panels, one class map each                                                         */
+    int image_panel;        /* 1: the untouched image is panel 0 and the overlays follow (show_img); 0: overlays only          */
+    int gap;                /* black columns between panels (the reference's pivot: 15)                                        */
+    int dst_pitch;          /* bytes per composite row, >= 3 * (W * P + gap * (P - 1))                                         */
+    int n_colors;           /* palette entries (n_colors x 3 bytes, RGB), 0..256                                               */
+    int background;         /* class index that is never coloured; -1: none (config.background)                                */
+    int write_ids;          /* 1: write the label-ID map of maps[0] through the 256-byte table lut                             */
+    int show255[FS_RENDER_MAX_PANELS];     /* per overlay panel: class 255 is painted black before the blend                   */
+    float alpha[FS_RENDER_MAX_PANELS], beta[FS_RENDER_MAX_PANELS];   /* per overlay panel: (float)w and (float)(1.0 - w)       */
+} fs_render_desc;
+fs_status fs_render_prediction(void* stream, const fs_render_desc* d, const unsigned char* image, const unsigned char* const maps[4],
+                               const unsigned char* palette, const unsigned char* lut, unsigned char* composite, unsigned char* ids);
 fs_status fs_exec_program(void* stream, const long long* words, long long n_words, const unsigned char* blob,
                           void* const* slots, int n_slots);
 /* Op word of every command: bits 0-15 the op code, bits 16-39 the stream lane (multi-stream form), bit 40 JOIN (ABI 208): this command
