@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfasterseg_hip.so")
 
-EXPECTED_ABI = 216          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
+EXPECTED_ABI = 217          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
 FS_F32, FS_BF16 = 0, 1
 FS_CONV_RELU, FS_CONV_TRANSPOSED, FS_CONV_ACCUM, FS_CONV_RELU_TAIL = 1, 2, 4, 8
 FS_CONV_KSPLIT, FS_CONV_NO_KSPLIT, FS_CONV_KSPLIT16 = 0x4000, 0x8000, 0x14000   # fs_conv3x3_s1_fwd: force / forbid the K-split form (16: 16-channel tiles)
@@ -145,9 +145,12 @@ SIGNATURES = {
     "fs_weighted_sum_dots": [c_vp, c_ll, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp],
     "fs_ohem_ce_fwd": [c_vp, c_vp, c_vp, c_ll, c_int, c_ll, c_int, c_vp, c_vp, c_vp],
     "fs_ohem_ce_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_ll, c_vp],
+    "fs_ohem_ce_bwd_coef": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_ll, c_vp],
+    "fs_ohem_select": [c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_vp, c_float, c_ll, c_vp, c_vp, c_vp, c_vp, c_ll],
     "fs_kl_distill_fwd": [c_vp, c_vp, c_vp, c_ll, c_int, c_ll, c_vp, c_vp, c_vp],
     "fs_ohem_ce_up_fwd": [c_vp, ctypes.POINTER(LogitsDesc), c_vp, c_vp, c_int, c_vp, c_vp, c_vp],
     "fs_ohem_ce_up_bwd": [c_vp, ctypes.POINTER(LogitsDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll],
+    "fs_ohem_ce_up_bwd_coef": [c_vp, ctypes.POINTER(LogitsDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll],
     "fs_kl_distill_up_fwd": [c_vp, ctypes.POINTER(LogitsDesc), c_vp, ctypes.POINTER(LogitsDesc), c_vp, c_vp, c_vp, c_vp],
     "fs_kl_distill_up_bwd": [c_vp, ctypes.POINTER(LogitsDesc), c_vp, ctypes.POINTER(LogitsDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                              c_ll],
@@ -168,6 +171,7 @@ _SPECIAL = {
     "fs_sgd_chunk_elems": ([], c_int),
     "fs_sgd_tensor_chunks": ([c_ll, c_int, c_int, c_int], c_ll),
     "fs_loss_up_workspace_bytes": ([ctypes.POINTER(LogitsDesc)], c_ll),
+    "fs_ohem_select_workspace_bytes": ([c_ll], c_ll),
     "fs_train_batch_args_bytes": ([c_int], c_ll),
     "fs_zoom_cell_supported": ([ctypes.POINTER(ZoomDesc)], c_int),
     "fs_workspace_counter_bytes": ([], c_ll),

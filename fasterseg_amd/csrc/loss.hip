@@ -4,8 +4,9 @@
 // tools/seg_opr/loss_opr.py:63-93) in the student distillation step (train/train.py:256-259): at 12 x 19 x 512 x 1024
 // logits are 478 MB per head, and the ATen chain moves that tensor ~10 times (softmax out, transposed copy, log_softmax out,
 // nll, and their backwards).  Here the forward reads the logits once and emits two per-pixel vectors (probability of the
-// true class, log-sum-exp); the hard-example threshold is still found with a device sort of that vector; the backward reads
-// the logits once more and writes d logits = kept * (softmax - onehot) * scale directly.
+// true class, log-sum-exp); the hard-example threshold of the unweighted criterion is still found with a device sort of that
+// vector (the class-weighted criterion selects with ohem_select.hip); the backward reads the logits once more and writes
+// d logits = kept * (softmax - onehot) * scale directly (kept: a byte, or fs_ohem_select's per-pixel coefficient).
 #include "common.h"
 
 namespace fs {
@@ -31,20 +32,26 @@ __global__ __launch_bounds__(256) void ohem_ce_fwd_kernel(const float* __restric
     }
 }
 
+// KT = unsigned char: the kept byte of the unweighted criterion; KT = float: the per-pixel coefficient of fs_ohem_select (the kept
+// pixel's class weight, 0 for a dropped one), which scales the pixel's gradient
+template <typename KT>
 __global__ __launch_bounds__(256) void ohem_ce_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
-                                                          const float* __restrict__ lse, const unsigned char* __restrict__ kept,
+                                                          const float* __restrict__ lse, const KT* __restrict__ kept,
                                                           const float* __restrict__ scale, int C, long long HW, long long P,
                                                           float* __restrict__ dlogits) {
+    constexpr bool COEF = sizeof(KT) == sizeof(float);
     const float g = *scale;
     for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < P; p += (long long)gridDim.x * blockDim.x) {
         const long long b = p / HW, hw = p - b * HW;
         const long long off = b * C * HW + hw;
-        const bool k = kept[p] != 0;
+        const KT kv = kept[p];
+        const bool k = kv != 0;
+        const float gk = COEF ? g * (float)kv : g;
         const float l = lse[p];
         const long long t = target[p];
         for (int c = 0; c < C; ++c) {
             float d = 0.f;
-            if (k) d = (expf(logits[off + (long long)c * HW] - l) - (c == t ? 1.f : 0.f)) * g;
+            if (k) d = (expf(logits[off + (long long)c * HW] - l) - (c == t ? 1.f : 0.f)) * gk;
             __builtin_nontemporal_store(d, dlogits + off + (long long)c * HW);
         }
     }
@@ -144,7 +151,19 @@ extern "C" fs_status fs_ohem_ce_bwd(void* stream, const float* logits, const lon
     const long long P = B * HW;
     long long blocks = (P + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    FS_LAUNCH(ohem_ce_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, target, lse, kept, scale,
-                       C, HW, P, dlogits);
+    FS_LAUNCH((ohem_ce_bwd_kernel<unsigned char>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, target, lse, kept,
+                       scale, C, HW, P, dlogits);
     return check_launch("fs_ohem_ce_bwd");
+}
+
+extern "C" fs_status fs_ohem_ce_bwd_coef(void* stream, const float* logits, const long long* target, const float* lse,
+                                         const float* coef, const float* scale, long long B, int C, long long HW, float* dlogits) {
+    FS_REQUIRE(logits && target && lse && coef && scale && dlogits && B > 0 && C > 0 && HW > 0, FS_ERR_INVALID,
+               "fs_ohem_ce_bwd_coef: bad argument");
+    const long long P = B * HW;
+    long long blocks = (P + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    FS_LAUNCH((ohem_ce_bwd_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, target, lse, coef, scale,
+                       C, HW, P, dlogits);
+    return check_launch("fs_ohem_ce_bwd_coef");
 }

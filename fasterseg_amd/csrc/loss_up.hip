@@ -122,11 +122,13 @@ __device__ __forceinline__ int first_dst(float scale, int i, int out_size) {
 // resident and every per-pixel load (lse, target, kept) was an exposed HBM round trip - 1.2 ms per x8 head.
 // UNIFORM: `lo` has the cell geometry, its four corner vectors are loaded once; otherwise (a teacher map of another resolution)
 // the logits of every pixel are interpolated from `lo` / `gl` with loads.
-template <typename T, bool OHEM, bool UNIFORM>
+// KT: the kept byte of the unweighted criterion, or (float) fs_ohem_select's per-pixel coefficient, which scales the pixel's terms.
+template <typename T, bool OHEM, bool UNIFORM, typename KT = unsigned char>
 __device__ __forceinline__ void cell_sweep(float (&S)[16], float sign, int c0, const T* __restrict__ lo, const UpGeom& gl,
                                            const UpGeom& g, int n, int i, int j, int Ya, int ny, int Xa, int nx, int first, int step,
                                            const float* __restrict__ lse, const long long* __restrict__ target,
-                                           const unsigned char* __restrict__ kept) {
+                                           const KT* __restrict__ kept) {
+    constexpr bool COEF = sizeof(KT) == sizeof(float);
     float L[4][4];
     if (UNIFORM) {
         const int i1 = i + (i < g.h - 1 ? 1 : 0), j1 = j + (j < g.w - 1 ? 1 : 0);
@@ -143,7 +145,11 @@ __device__ __forceinline__ void cell_sweep(float (&S)[16], float sign, int c0, c
         const int Y = Ya + dy_, X = Xa + (k - dy_ * nx);
         const long long p = ((long long)n * g.H + Y) * g.W + X;
         const float l = lse[p];
-        const float keep = OHEM ? (kept[p] ? sign : 0.f) : sign;
+        float keep = sign;
+        if (OHEM) {
+            const KT kv = kept[p];
+            keep = COEF ? sign * (float)kv : (kv ? sign : 0.f);
+        }
         const int t = OHEM ? (int)target[p] : -1;
         const Tap th = make_tap(g.rh, Y, g.h), tw = make_tap(g.rw, X, g.w);
         float v[4];
@@ -175,11 +181,11 @@ __device__ __forceinline__ void cell_sweep(float (&S)[16], float sign, int c0, c
 }
 
 // WAVES = 1: four cells per block, one wave each; WAVES = 4: one cell per block.  KL: second sweep over the teacher.
-template <typename TS, typename TT, bool OHEM, int WAVES>
+template <typename TS, typename TT, bool OHEM, int WAVES, typename KT = unsigned char>
 __global__ __launch_bounds__(256) void up_bwd_cells_kernel(const TS* __restrict__ s_lo, UpGeom g, const TT* __restrict__ t_lo, UpGeom gt,
                                                            const float* __restrict__ lse_s, const float* __restrict__ lse_t,
                                                            const long long* __restrict__ target,
-                                                           const unsigned char* __restrict__ kept, float* __restrict__ ws) {
+                                                           const KT* __restrict__ kept, float* __restrict__ ws) {
     __shared__ float part[4][16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long cells = (long long)g.N * g.h * g.w;
@@ -198,10 +204,10 @@ __global__ __launch_bounds__(256) void up_bwd_cells_kernel(const TS* __restrict_
         float S[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) S[k] = 0.f;
-        cell_sweep<TS, OHEM, true>(S, 1.f, c0, s_lo, g, g, n, i, j, Ya, ny, Xa, nx, first, step, lse_s, target, kept);
+        cell_sweep<TS, OHEM, true, KT>(S, 1.f, c0, s_lo, g, g, n, i, j, Ya, ny, Xa, nx, first, step, lse_s, target, kept);
         if (!OHEM) {
-            if (same) cell_sweep<TT, false, true>(S, -1.f, c0, t_lo, gt, g, n, i, j, Ya, ny, Xa, nx, first, step, lse_t, nullptr, nullptr);
-            else cell_sweep<TT, false, false>(S, -1.f, c0, t_lo, gt, g, n, i, j, Ya, ny, Xa, nx, first, step, lse_t, nullptr, nullptr);
+            if (same) cell_sweep<TT, false, true>(S, -1.f, c0, t_lo, gt, g, n, i, j, Ya, ny, Xa, nx, first, step, lse_t, nullptr, (const unsigned char*)nullptr);
+            else cell_sweep<TT, false, false>(S, -1.f, c0, t_lo, gt, g, n, i, j, Ya, ny, Xa, nx, first, step, lse_t, nullptr, (const unsigned char*)nullptr);
         }
 #pragma unroll
         for (int k = 0; k < 16; ++k) S[k] = wave_sum(S[k]);
@@ -330,17 +336,17 @@ extern "C" long long fs_loss_up_workspace_bytes(const fs_logits_desc* d) {
 }
 
 // cells + gather launches of one backward; `big` cells (more than two wave iterations of pixels) take a whole block
-template <typename TS, typename TT, bool OHEM>
+template <typename TS, typename TT, bool OHEM, typename KT = unsigned char>
 static void launch_up_bwd(hipStream_t st, const UpGeom& g, const void* s_lo, const UpGeom& gt, const void* t_lo, const float* lse_s,
-                          const float* lse_t, const long long* target, const unsigned char* kept, const float* scale, float* ws,
+                          const float* lse_t, const long long* target, const KT* kept, const float* scale, float* ws,
                           void* dlo) {
     const long long cells = (long long)g.N * g.h * g.w;
     const double area = ((double)g.H / g.h) * ((double)g.W / g.w);
     if (area <= 100.0)           // x8 heads: cells of 8-9 x 8-9 pixels, one wave each
-        FS_LAUNCH((up_bwd_cells_kernel<TS, TT, OHEM, 1>), dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, st, (const TS*)s_lo, g,
+        FS_LAUNCH((up_bwd_cells_kernel<TS, TT, OHEM, 1, KT>), dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, st, (const TS*)s_lo, g,
                            (const TT*)t_lo, gt, lse_s, lse_t, target, kept, ws);
     else                         // x16 / x32: 17 x 17 / 33 x 33 pixels over a block
-        FS_LAUNCH((up_bwd_cells_kernel<TS, TT, OHEM, 4>), dim3((unsigned)cells), dim3(256), 0, st, (const TS*)s_lo, g,
+        FS_LAUNCH((up_bwd_cells_kernel<TS, TT, OHEM, 4, KT>), dim3((unsigned)cells), dim3(256), 0, st, (const TS*)s_lo, g,
                            (const TT*)t_lo, gt, lse_s, lse_t, target, kept, ws);
     FS_LAUNCH((up_bwd_gather_kernel<TS>), dim3(pixel_blocks(cells * g.cs)), dim3(256), 0, st, ws, g, scale, (TS*)dlo);
 }
@@ -359,6 +365,22 @@ extern "C" fs_status fs_ohem_ce_up_bwd(void* stream, const fs_logits_desc* d, co
     else
         launch_up_bwd<bf16_t, bf16_t, true>(st, g, logits_lo, g, nullptr, lse, nullptr, target, kept, scale, workspace, dlogits_lo);
     return check_launch("fs_ohem_ce_up_bwd");
+}
+
+extern "C" fs_status fs_ohem_ce_up_bwd_coef(void* stream, const fs_logits_desc* d, const void* logits_lo, const long long* target,
+                                            const float* lse, const float* coef, const float* scale, void* dlogits_lo,
+                                            float* workspace, long long workspace_bytes) {
+    UpGeom g;
+    FS_REQUIRE(make_geom(d, g), FS_ERR_INVALID, "fs_ohem_ce_up_bwd_coef: bad descriptor");
+    FS_REQUIRE(logits_lo && target && lse && coef && scale && dlogits_lo, FS_ERR_INVALID, "fs_ohem_ce_up_bwd_coef: null argument");
+    FS_REQUIRE(workspace && workspace_bytes >= fs_loss_up_workspace_bytes(d), FS_ERR_INVALID,
+               "fs_ohem_ce_up_bwd_coef: workspace of %lld bytes needed (fs_loss_up_workspace_bytes)", fs_loss_up_workspace_bytes(d));
+    hipStream_t st = (hipStream_t)stream;
+    if (d->dtype == FS_F32)
+        launch_up_bwd<float, float, true, float>(st, g, logits_lo, g, nullptr, lse, nullptr, target, coef, scale, workspace, dlogits_lo);
+    else
+        launch_up_bwd<bf16_t, bf16_t, true, float>(st, g, logits_lo, g, nullptr, lse, nullptr, target, coef, scale, workspace, dlogits_lo);
+    return check_launch("fs_ohem_ce_up_bwd_coef");
 }
 
 extern "C" fs_status fs_kl_distill_up_fwd(void* stream, const fs_logits_desc* ds, const void* student_lo, const fs_logits_desc* dt,
@@ -391,7 +413,7 @@ extern "C" fs_status fs_kl_distill_up_bwd(void* stream, const fs_logits_desc* ds
     FS_REQUIRE(workspace && workspace_bytes >= fs_loss_up_workspace_bytes(ds), FS_ERR_INVALID,
                "fs_kl_distill_up_bwd: workspace of %lld bytes needed (fs_loss_up_workspace_bytes)", fs_loss_up_workspace_bytes(ds));
     hipStream_t st = (hipStream_t)stream;
-#define FS_KL_BWD(TS, TT) launch_up_bwd<TS, TT, false>(st, gs, student_lo, gt, teacher_lo, lse_s, lse_t, nullptr, nullptr, scale, workspace, d_student_lo)
+#define FS_KL_BWD(TS, TT) launch_up_bwd<TS, TT, false>(st, gs, student_lo, gt, teacher_lo, lse_s, lse_t, nullptr, (const unsigned char*)nullptr, scale, workspace, d_student_lo)
     if (ds->dtype == FS_F32 && dt->dtype == FS_F32) FS_KL_BWD(float, float);
     else if (ds->dtype == FS_F32) FS_KL_BWD(float, bf16_t);
     else if (dt->dtype == FS_F32) FS_KL_BWD(bf16_t, float);

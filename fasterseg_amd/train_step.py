@@ -18,7 +18,7 @@ from .parallel import FlatGradientSync, broadcast_parameters
 
 class StudentDistillStep:
     def __init__(self, batch, height, width, lr=0.01, momentum=0.9, weight_decay=5e-4, teacher_engine_dtype=None, seed=12345,
-                 device="cuda", compute_dtype=torch.float32, fused_loss=None, arch_states=None):
+                 device="cuda", compute_dtype=torch.float32, fused_loss=None, arch_states=None, class_weight=None):
         self.device = torch.device(device)
         self.compute_dtype = compute_dtype      # activation storage / MFMA operand type; master weights, BN statistics,
         # accumulators and gradients of parameters stay fp32
@@ -29,7 +29,11 @@ class StudentDistillStep:
         broadcast_parameters(self.student)
         broadcast_parameters(self.teacher)
         min_kept = int(batch * height * width // 16)                       # train/train.py:62 with gt_down_sampling = 1
-        self.ohem = ProbOhemCrossEntropy2d(ignore_label=255, thresh=0.7, min_kept=min_kept, use_weight=False)
+        # class_weight: one value per class for the criterion's weighted mean (the reference's use_weight=True takes its own Cityscapes
+        # table, tools/seg_opr/loss_opr.py:51-58; none is shipped here), None: the unweighted criterion of train/train.py:62
+        self.class_weight = class_weight
+        self.ohem = ProbOhemCrossEntropy2d(ignore_label=255, thresh=0.7, min_kept=min_kept, use_weight=class_weight is not None,
+                                           weight=class_weight)
         self.sync = FlatGradientSync(self.student.parameters(), bucket_mb=4, average="defer")      # 17.6 MB -> 5 buckets, overlapped with backward
         self.optimizer = FlatSGD(self.sync, lr, momentum, weight_decay, pack_dtype=compute_dtype)       # train/train.py:173-176
         self.lamb = 0.2
@@ -76,7 +80,7 @@ class StudentDistillStep:
         buffers = list(self.student.buffers())
         saved = [b_.clone() for b_ in buffers]
         ohem = ProbOhemCrossEntropy2d(ignore_label=255, thresh=0.7, min_kept=int(imgs.shape[0] * self.size[0] * self.size[1] // 16),
-                                      use_weight=False)
+                                      use_weight=self.class_weight is not None, weight=self.class_weight)
         with torch.no_grad():
             FN.set_compute_dtype(self.compute_dtype)
             try:

@@ -93,7 +93,7 @@ typedef struct fs_resize_desc {
 const char* fs_last_error(void);
 /* ABI revision of this header; fs_version() returns the one the library was built from.  Bindings check both this and
  * fs_struct_size() when they load the library (fasterseg_amd/_lib.py) - a stale .so must not be used silently. */
-#define FS_ABI_VERSION 216
+#define FS_ABI_VERSION 217
 int fs_version(void);
 /* Bit-reproducible mode (default off; FS_DETERMINISTIC=1 in the environment turns it on at load): every cross-block reduction that
  * otherwise uses float atomics - the pixel slabs of fs_conv2d_wgrad_ws, BatchNorm statistics and parameter gradients of maps above
@@ -414,6 +414,35 @@ fs_status fs_ohem_ce_fwd(void* stream, const float* logits, const long long* tar
 fs_status fs_ohem_ce_bwd(void* stream, const float* logits, const long long* target, const float* lse, const unsigned char* kept,
                          const float* scale, long long B, int C, long long HW, float* dlogits);
 
+/* The same backward with a per-pixel coefficient in place of the kept byte (ABI 217, the class-weighted criterion):
+ * dlogits[b][c][hw] = coef[p] * (exp(logit - lse[p]) - [c == target[p]]) * (*scale); a pixel with coef[p] == 0 contributes nothing. */
+fs_status fs_ohem_ce_bwd_coef(void* stream, const float* logits, const long long* target, const float* lse, const float* coef,
+                              const float* scale, long long B, int C, long long HW, float* dlogits);
+
+/* --- OHEM hard-example selection + class-weighted reduction on the device (ABI 217) ----------------------------------- */
+/* What the criterion does between fs_ohem_ce[_up]_fwd and its backward (tools/seg_opr/loss_opr.py:66-93 with the class-weighted
+ * CrossEntropyLoss of :51-58), from the per-pixel vectors those kernels write (ignored pixels: true_prob = 1, nll = 0):
+ *   valid[p]  = target[p] != ignore and 0 <= target[p] < C      (a label outside [0, C) that is not `ignore` counts as ignored)
+ *   min_kept > 0:  k = min(P, min_kept), kth = the k-th smallest of ALL P entries of true_prob (ignored pixels take part at 1.0),
+ *                  threshold = max(thresh, kth), apply = num_valid >= min_kept and num_valid > 0,
+ *                  kept[p] = valid[p] and (true_prob[p] <= threshold or not apply)
+ *   min_kept == 0: kept = valid (the reference builds no mask), threshold = thresh and apply = 0 are reported
+ *   coef[p] = kept[p] ? class_weight[target[p]] : 0      (class_weight: C floats on the device, or NULL = all 1)
+ *   result  = {num / den, den, threshold, apply ? 1 : 0} with den = sum coef, num = sum coef * nll (0 / 0 = NaN, as in the torch chain)
+ *   counts  = {num_valid, num_kept}
+ * kth is exact (bit-identical to a sort): a most-significant-digit-first radix select over the 32-bit pattern in three histogram
+ * passes of 11 / 11 / 10 bits.  Probabilities are non-negative, so their patterns order as unsigned integers; any other pattern (a NaN,
+ * a negative number) orders by its bits and indexes nothing out of range; a NaN kth gives a NaN threshold and an empty kept set.
+ * Six launches with selection, two without, nothing read back, no memset node (the entry point clears its own histograms with a
+ * kernel; `workspace` need not be zeroed).  Histograms are per-block LDS counts flushed with integer atomics; num and den are
+ * per-block fp64 partials summed in a fixed order by one block: no float atomics, results are bit-identical from run to run.
+ * true_prob / nll / coef / target: 4- / 8-byte aligned; 16-byte accesses where the pointers allow it, scalar head and tail.
+ * C in 1..20; workspace of fs_ohem_select_workspace_bytes(P) bytes, 8-byte aligned. */
+long long fs_ohem_select_workspace_bytes(long long P);
+fs_status fs_ohem_select(void* stream, const float* true_prob, const float* nll, const long long* target, long long P, int C, int ignore,
+                         const float* class_weight, float thresh, long long min_kept, float* coef, float* result, long long* counts,
+                         void* workspace, long long workspace_bytes);
+
 /* KL distillation term nn.KLDivLoss()(log_softmax(student), softmax(teacher)) (train/train.py:64,260) on (B, C, HW) fp32
  * logits: kl[p] = sum_c p_t (log p_t - log p_s) per pixel plus both log-sum-exps; the caller sums kl and divides by the
  * element count ('mean' reduction).  Backward: d_student = (softmax(student) - softmax(teacher)) * (*scale). */
@@ -509,6 +538,10 @@ long long fs_loss_up_workspace_bytes(const fs_logits_desc* d);
 fs_status fs_ohem_ce_up_bwd(void* stream, const fs_logits_desc* d, const void* logits_lo, const long long* target, const float* lse,
                             const unsigned char* kept, const float* scale, void* dlogits_lo, float* workspace,
                             long long workspace_bytes);
+/* the same two launches with a per-pixel coefficient (fs_ohem_select's coef) in place of the kept byte (ABI 217):
+ * dlogits_lo[n,i,j,c] = (*scale) * sum over pixels p of coef[p] * w(p -> i,j) * (softmax_c(p) - [c == target p]) */
+fs_status fs_ohem_ce_up_bwd_coef(void* stream, const fs_logits_desc* d, const void* logits_lo, const long long* target, const float* lse,
+                                 const float* coef, const float* scale, void* dlogits_lo, float* workspace, long long workspace_bytes);
 /* student and teacher may come at different low resolutions / dtypes; both are up-sampled to the same (H, W) */
 fs_status fs_kl_distill_up_fwd(void* stream, const fs_logits_desc* ds, const void* student_lo, const fs_logits_desc* dt,
                                const void* teacher_lo, float* kl, float* lse_s, float* lse_t);
