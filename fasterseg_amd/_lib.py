@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfasterseg_hip.so")
 
-EXPECTED_ABI = 217          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
+EXPECTED_ABI = 218          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
 FS_F32, FS_BF16 = 0, 1
 FS_CONV_RELU, FS_CONV_TRANSPOSED, FS_CONV_ACCUM, FS_CONV_RELU_TAIL = 1, 2, 4, 8
 FS_CONV_KSPLIT, FS_CONV_NO_KSPLIT, FS_CONV_KSPLIT16 = 0x4000, 0x8000, 0x14000   # fs_conv3x3_s1_fwd: force / forbid the K-split form (16: 16-channel tiles)
@@ -75,6 +75,14 @@ class KernelTime(ctypes.Structure):
 
 class SgdTensor(ctypes.Structure):
     _fields_ = [("p", c_vp), ("g_off", c_ll), ("numel", c_ll), ("I", c_int), ("taps", c_int), ("pack_fwd", c_vp), ("pack_flip", c_vp)]
+
+
+FS_REFRESH_PACK, FS_REFRESH_PACK_FRAG, FS_REFRESH_FOLD, FS_REFRESH_BIAS = 0, 1, 2, 3
+
+
+class RefreshEntry(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("kind", "dtype", "Cout", "Cin", "R", "S", "lo")] + [("eps", c_float), ("o_stride", c_ll), ("i_stride", c_ll)] + [
+        (n, c_vp) for n in ("src", "beta", "mean", "var", "dst", "shift")]
 
 
 # name -> argtypes (restype is int status unless listed in _SPECIAL); order = include/fasterseg_hip.h
@@ -159,6 +167,7 @@ SIGNATURES = {
     "fs_exec_program_streams": [c_vp, c_int, c_vp, c_ll, c_vp, c_vp, c_int],
     "fs_exec_program_group": [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int],
     "fs_sgd_momentum_multi": [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_float, c_float, c_float, c_int, c_int],
+    "fs_refresh_weights": [c_vp, c_vp, c_int, c_vp, c_int],
 }
 _SPECIAL = {
     "fs_last_error": ([], ctypes.c_char_p),
@@ -170,6 +179,8 @@ _SPECIAL = {
     "fs_packed_weight_frag_elems": ([c_int, c_int, c_int], c_ll),
     "fs_sgd_chunk_elems": ([], c_int),
     "fs_sgd_tensor_chunks": ([c_ll, c_int, c_int, c_int], c_ll),
+    "fs_refresh_chunk_elems": ([], c_int),
+    "fs_refresh_entry_chunks": ([ctypes.POINTER(RefreshEntry)], c_ll),
     "fs_loss_up_workspace_bytes": ([ctypes.POINTER(LogitsDesc)], c_ll),
     "fs_ohem_select_workspace_bytes": ([c_ll], c_ll),
     "fs_train_batch_args_bytes": ([c_int], c_ll),
@@ -217,8 +228,8 @@ def lib():
         if got != EXPECTED_ABI:
             raise ImportError("libfasterseg_hip.so has ABI %d, these bindings expect %d: rebuild with `python -m fasterseg_amd.build "
                               "--force`" % (got, EXPECTED_ABI))
-        for which, struct in enumerate((ConvDesc, ResizeDesc, ZoomDesc, SgdTensor, LogitsDesc, EvalWindowDesc,
-                                           TrainSample, TrainBatchDesc, HeadsDesc, RenderDesc)):
+        for which, struct in list(enumerate((ConvDesc, ResizeDesc, ZoomDesc, SgdTensor, LogitsDesc, EvalWindowDesc,
+                                                TrainSample, TrainBatchDesc, HeadsDesc, RenderDesc))) + [(11, RefreshEntry)]:
             if handle.fs_struct_size(which) != ctypes.sizeof(struct):
                 raise ImportError("libfasterseg_hip.so: sizeof(%s) is %d in the library, %d in the bindings - stale build" % (
                     struct.__name__, handle.fs_struct_size(which), ctypes.sizeof(struct)))

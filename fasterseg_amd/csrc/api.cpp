@@ -43,6 +43,7 @@ extern "C" int fs_struct_size(int which) {
         case 7: return (int)sizeof(fs_train_batch_desc);
         case 8: return (int)sizeof(fs_heads_desc);
         case 9: return (int)sizeof(fs_render_desc);
+        case 11: return (int)sizeof(fs_refresh_entry);      // 10 stays unassigned (-1)
         default: return -1;
     }
 }

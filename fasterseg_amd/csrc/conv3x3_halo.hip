@@ -24,6 +24,7 @@
 // Replaces the stride-1 3x3 nn.Conv2d calls (+BatchNorm2d/ReLU) of reference search/operations.py:149-152,221-224,
 // 298-306,380-388, seg_oprs.py:22 — the layers that carry the FLOPs at >= 128x256 resolution.
 #include "common.h"
+#include "pack_index.h"
 
 namespace fs {
 
@@ -705,20 +706,9 @@ __global__ __launch_bounds__(256) void conv3x3_halo_ksplit16_kernel(HaloArgs p) 
 template <typename T>
 __global__ void pack_weight_frag_kernel(const float* __restrict__ w, long long o_stride, long long i_stride, int Cout, int Cin,
                                         int nchunks, long long total, T* __restrict__ out) {
-    constexpr int VEC = Elem<T>::VEC;
-    constexpr int CK = 4 * VEC;
     for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        long long t = idx;
-        const int e = (int)(t % VEC); t /= VEC;
-        const int lane = (int)(t % 64); t /= 64;
-        const int kk = (int)(t % 2); t /= 2;
-        const int tap = (int)(t % 9); t /= 9;
-        const int chunk = (int)(t % nchunks);
-        const int nt = (int)(t / nchunks);
-        const int co = nt * 32 + (lane & 31);
-        const int ci = chunk * CK + kk * (CK / 2) + (lane >> 5) * VEC + e;
-        float v = 0.f;
-        if (co < Cout && ci < Cin) v = w[co * o_stride + ci * i_stride + tap];
+        const long long src = pack_frag_src_offset<Elem<T>::VEC>(idx, o_stride, i_stride, Cout, Cin, nchunks);
+        const float v = src >= 0 ? w[src] : 0.f;
         Elem<T>::store(out + idx, v);
     }
 }
@@ -817,9 +807,7 @@ static int force_ks_of(int flags) {
 using namespace fs;
 
 extern "C" long long fs_packed_weight_frag_elems(int Cout, int Cin, int dtype) {
-    const int vec = vec_elems(dtype), ck = 4 * vec;
-    const long long ntiles = ((Cout + 127) / 128) * 4, nchunks = (Cin + ck - 1) / ck;   // whole 128-channel block tiles
-    return ntiles * nchunks * 9 * 2 * 64 * vec;
+    return pack_frag_elems(Cout, Cin, vec_elems(dtype));
 }
 
 extern "C" fs_status fs_pack_weight_frag(void* stream, const float* w, long long o_stride, long long i_stride, int Cout, int Cin,

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "group.h"
 #include "bn_bodies.h"
+#include "pack_index.h"
 
 namespace fs {
 
@@ -30,11 +31,7 @@ __global__ void pack_weight_kernel(const float* __restrict__ w, long long o_stri
         long long t = idx;
         float v;
         if (!tflip) {   // out[co][r][s][ci]
-            const int ci = divmod32(t, Cin);
-            const int s = divmod32(t, S);
-            const int r = divmod32(t, R);
-            const int co = (int)t;
-            v = w[co * o_stride + ci * i_stride + r * S + s];
+            v = w[pack_src_offset(idx, o_stride, i_stride, Cin, R, S)];
         } else {        // out[ci][R-1-r][S-1-s][co] = w[co][ci][r][s]
             const int co = divmod32(t, Cout);
             const int s2 = divmod32(t, S);

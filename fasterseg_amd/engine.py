@@ -137,7 +137,8 @@ class InferenceEngine:
                 json.dump(self._plan_out, f)
 
     # ---- 1. trace ----------------------------------------------------------------------------------
-    def _trace(self, net):
+    def _trace_ops(self, net):
+        """(ops, output symbol) of `net`'s forward on a shape-only input: host only, nothing is computed."""
         tracer = _Tracer(self.dtype)
         x = FN.SymTensor(self.input_shape, torch.float32, nchw=True)
         x.storage = ("input", 0)
@@ -148,8 +149,31 @@ class InferenceEngine:
         finally:
             FN._tracer = None
         assert isinstance(out, FN.SymTensor) and out.nchw, "network must end in the NCHW logits up-sample"
-        self.ops = tracer.ops
+        return tracer.ops, out
+
+    _SOURCE_FIELDS = ("weight", "w1", "w2", "bn", "bias")
+
+    @staticmethod
+    def _op_signature(op):
+        """What two traces must share for one plan to serve both networks (load_weights): the op, its output shape, where its
+        inputs come from and its convolution geometry.  Taken before the fusion passes rewrite the ops."""
+        ins = op["inputs"] if op["kind"] == "cat" else [op["x"]]
+        return (op["kind"], tuple(op["out"].shape), tuple(s_.producer for s_ in ins)) + tuple(
+            op.get(k) for k in ("cout", "cin", "k", "stride", "pad", "relu", "half", "out_nchw"))
+
+    def _trace(self, net):
+        self.ops, out = self._trace_ops(net)
         self.out_sym = out
+        # for load_weights: the traced ops hold the network's parameter and running-statistics tensors by reference
+        self._sources = list(self.ops)
+        self._signature = [self._op_signature(op) for op in self.ops]
+        self._source_slot = {}                     # id(tensor or bn tuple) -> (op index, field)
+        for i, op in enumerate(self.ops):
+            for f in self._SOURCE_FIELDS:
+                if op.get(f) is not None:
+                    self._source_slot.setdefault(id(op[f]), (i, f))
+        self._refresh = []                         # one record per weight-derived buffer the plan keeps alive
+        self._refresh_tab = None
         if self.output_mode == "lowres":
             last = self.ops[out.producer]
             assert last["kind"] == "resize" and last["out_nchw"]
@@ -379,9 +403,21 @@ class InferenceEngine:
             scale, shift = scale[lo:lo + cout].contiguous().to(self.device), shift[lo:lo + cout].contiguous().to(self.device)
         else:
             scale = None
-            shift = bias.detach().float()[:cout].contiguous().to(self.device) if bias is not None else None
+            # copy=True: for a network already on the device every step of this chain returns a view of the parameter itself, and
+            # load_weights must never write into the network it reads from
+            shift = bias.detach().float()[:cout].contiguous().to(self.device, copy=True) if bias is not None else None
         self._keep += [scale, shift]
+        if bn is not None:
+            self._record(_lib.FS_REFRESH_FOLD, bn, scale, shift, cout=cout, lo=lo)
+        elif bias is not None:
+            self._record(_lib.FS_REFRESH_BIAS, bias, None, shift, cout=cout)
         return scale, shift
+
+    def _record(self, kind, source, dst, shift=None, **kw):
+        """Remember how a kept buffer derives from the network (`source`: the weight / bias tensor or BatchNorm tuple of a traced op)."""
+        if kind in (_lib.FS_REFRESH_PACK, _lib.FS_REFRESH_PACK_FRAG):
+            kw["dst_taps"] = tuple(source.shape[2:])
+        self._refresh.append(dict(kind=kind, slot=self._source_slot[id(source)], dst=dst, shift=shift, **kw))
 
     def _add_conv(self, x, out, weight, scale, shift, k, stride, pad, relu, cout, cin, out_off=0, label="conv", vres=None, vres_halo=False):
         N, _, H, W = x.shape
@@ -438,6 +474,7 @@ class InferenceEngine:
             self.autotuned.append((label, N * H * W, cin, cout, best[1], [(nm, round(t * 1e3, 2)) for t, nm, _ in timed]))
             fn, args, wp, dsel = best[2]
         self._keep.append(wp)
+        self._record(_lib.FS_REFRESH_PACK_FRAG if fn == "fs_conv3x3_s1_fwd" else _lib.FS_REFRESH_PACK, weight, wp, cout=cout, cin=cin, dtype=self.dtype)
         es = 2 if self.dtype == torch.bfloat16 else 4
         flops = 2.0 * N * Ho * Wo * cout * cin * k * k
         in_px = N * (src_hw[0] * src_hw[1] if src_hw else H * W)
@@ -514,6 +551,8 @@ class InferenceEngine:
         w1 = K.pack_weight_frag(A["weight"].detach().to(self.device), self.dtype, cmid, cin)
         w2 = K.pack_weight_frag(B["weight"].detach().to(self.device), self.dtype, cout, cmid)
         self._keep += [d, w1, w2]
+        self._record(_lib.FS_REFRESH_PACK_FRAG, A["weight"], w1, cout=cmid, cin=cin, dtype=self.dtype)
+        self._record(_lib.FS_REFRESH_PACK_FRAG, B["weight"], w2, cout=cout, cin=cmid, dtype=self.dtype)
         args = (ctypes.byref(d), ctypes.c_void_p(xp), ctypes.c_void_p(w1.data_ptr()), K._p(sc1), K._p(sh1), ctypes.c_void_p(w2.data_ptr()),
                 K._p(sc2), K._p(sh2), ctypes.c_void_p(yp))
         flops = 2.0 * N * d.h * d.w * 9 * (cin * cmid + cmid * cout)
@@ -607,6 +646,7 @@ class InferenceEngine:
                 scale, shift = self._fold(op["bn"], None, cout)
                 wp = K.pack_weight(op["weight"].detach().to(self.device), torch.float32)
                 self._keep.append(wp)
+                self._record(_lib.FS_REFRESH_PACK, op["weight"], wp, cout=cout, cin=op["weight"].shape[1], dtype=torch.float32)
                 yp, y_cs = self._ptr(out)
                 args = (N, H, W, cout, ctypes.c_void_p(self.input.data_ptr()), ctypes.c_void_p(wp.data_ptr()), K._p(scale), K._p(shift),
                         ctypes.c_void_p(yp), y_cs, K.dtype_code(self.dtype), int(op["relu"]))
@@ -826,6 +866,132 @@ class InferenceEngine:
         self.calls = calls
         self._finish_lanes()
         return max(finish)
+
+    # ---- 3c. same architecture, new numbers: rewrite every weight-derived buffer in place --------------------------------
+    # The reference validates the model it is training (train/train.py:196-208 after the first and every tenth epoch,
+    # search/train_search.py:141-183 after every epoch) and loads a trained teacher into an existing model
+    # (train/train.py:124-135).  A built engine follows such a change with ONE fs_refresh_weights launch (refresh.hip) over the
+    # buffers recorded while lowering: no buffer moves, the plan, the launch program and the captured graph stay as they are.
+    def _on_device(self, t):
+        index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        return t.device.type == self.device.type and t.device.index == index
+
+    def _staged(self, key, t, filt=False):
+        """`t` as fp32 device memory the refresh kernel can read: the tensor itself where it already is that (a parameter of a
+        network on this device), else a staging buffer kept per source that `t` is copied into (as the constructor's `.to(device)`)."""
+        t = t.detach()
+        if self._on_device(t) and t.dtype == torch.float32 and (
+                (t.stride(3) == 1 and t.stride(2) == t.shape[3]) if filt else t.is_contiguous()):
+            return t
+        buf = self._stages.get(key)
+        if buf is None or buf.shape != t.shape:
+            buf = self._stages[key] = torch.empty(tuple(t.shape), dtype=torch.float32, device=self.device)
+        buf.copy_(t)
+        return buf
+
+    def _check_sources(self, sources):
+        """Every recorded buffer can be derived from `sources` (same traced ops, possibly of another module): raises before a byte is written."""
+        for r in self._refresh:
+            i, f = r["slot"]
+            src = sources[i][f]
+            what = "op %d (%s) %s" % (i, sources[i]["kind"], f)
+            if r["kind"] in (_lib.FS_REFRESH_PACK, _lib.FS_REFRESH_PACK_FRAG):
+                if src.dim() != 4 or src.shape[0] < r["cout"] or src.shape[1] < r["cin"] or tuple(src.shape[2:]) != tuple(r["dst_taps"]):
+                    raise ValueError("load_weights: %s has shape %s, the plan packs %d x %d x %s" % (
+                        what, tuple(src.shape), r["cout"], r["cin"], tuple(r["dst_taps"])))
+            elif r["kind"] == _lib.FS_REFRESH_FOLD:
+                if any(v.numel() < r["lo"] + r["cout"] for v in src[:4]):
+                    raise ValueError("load_weights: %s has fewer than %d channels" % (what, r["lo"] + r["cout"]))
+            elif src.numel() < r["cout"]:
+                raise ValueError("load_weights: %s has fewer than %d values" % (what, r["cout"]))
+
+    def _refresh_table(self):
+        """The device tables of fs_refresh_weights, built once: one fs_refresh_entry per recorded buffer (host mirror kept for
+        rebinding sources) and the (entry, chunk) pairs of its blocks."""
+        if self._refresh_tab is not None:
+            return self._refresh_tab
+        lib = _lib.lib()
+        n = len(self._refresh)
+        host = torch.zeros(max(1, n) * ctypes.sizeof(_lib.RefreshEntry), dtype=torch.uint8)
+        entries = (_lib.RefreshEntry * n).from_address(host.data_ptr())
+        for e, r in zip(entries, self._refresh):
+            e.kind, e.Cout, e.Cin, e.R, e.S, e.lo = r["kind"], r["cout"], r.get("cin", 0), 1, 1, r.get("lo", 0)
+            if "dtype" in r:
+                e.dtype = K.dtype_code(r["dtype"])
+                e.R, e.S = r["dst_taps"]
+            e.dst = r["dst"].data_ptr() if r["dst"] is not None else None
+            e.shift = r["shift"].data_ptr() if r["shift"] is not None else None
+        self._stages = {}
+        self._refresh_tab = tab = dict(host=host, entries=entries, dev=torch.empty_like(host, device=self.device))
+        self._bind_sources()
+        chunks, nbytes = [], 0
+        for t, (e, r) in enumerate(zip(entries, self._refresh)):
+            c = lib.fs_refresh_entry_chunks(ctypes.byref(e))
+            if c < 0:
+                self._refresh_tab = None
+                raise _lib.FasterSegHipError("fs_refresh_entry_chunks: %s" % lib.fs_last_error().decode())
+            chunks += [(t, k) for k in range(c)]
+            elems = r["cout"] * r.get("cin", 1) * e.R * e.S
+            nbytes += 4 * elems * (4 if r["kind"] == _lib.FS_REFRESH_FOLD else 1)
+            nbytes += sum(b.numel() * b.element_size() for b in (r["dst"], r["shift"]) if b is not None)
+        tab["n_chunks"] = len(chunks)
+        tab["chunks"] = torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(self.device)
+        tab["bytes"] = nbytes                      # algorithmic: every source element read once, every destination written once
+        tab["dev"].copy_(host)
+        return tab
+
+    def _bind_sources(self):
+        """Point every entry at its current source (staging what is not fp32 device memory); True if the host table changed."""
+        changed = False
+        for e, r in zip(self._refresh_tab["entries"], self._refresh):
+            i, f = r["slot"]
+            src = self._sources[i][f]
+            if r["kind"] == _lib.FS_REFRESH_FOLD:
+                ptrs = [self._staged((i, f, j), v).data_ptr() for j, v in enumerate(src[:4])]     # gamma, beta, mean, var
+                new = (ptrs[0], ptrs[1], ptrs[2], ptrs[3], 0, 0, float(src[4]))
+            elif r["kind"] == _lib.FS_REFRESH_BIAS:
+                new = (self._staged((i, f), src).data_ptr(), None, None, None, 0, 0, 0.0)
+            else:
+                w = self._staged((i, f), src, filt=True)
+                new = (w.data_ptr(), None, None, None, w.stride(0), w.stride(1), 0.0)
+            old = (e.src, e.beta, e.mean, e.var, e.o_stride, e.i_stride, e.eps)
+            if old != (new[:6] + (ctypes.c_float(new[6]).value,)):
+                e.src, e.beta, e.mean, e.var, e.o_stride, e.i_stride, e.eps = new
+                changed = True
+        return changed
+
+    def load_weights(self, net=None):
+        """Follow a change of the weights without rebuilding: every filter pack, folded BatchNorm scale / shift and bias the plan
+        keeps (selected variant or not) is rewritten in place by one fs_refresh_weights launch on the current stream, i.e. behind
+        the frames already issued there and ahead of the next.
+
+        net=None re-reads the tensors recorded at trace time: the model the engine was built from (or last rebound to) after its
+        parameters were updated in place, e.g. by an optimizer (call `.eval()` on it as for the constructor).  net=<module> rebinds
+        to another module of the same architecture: it is traced (host only) and must give the same op list, else ValueError
+        names the first difference before anything is written.  Tensors that are not fp32 memory of the engine's device are
+        staged to it first.  Nothing is re-timed, re-captured or reallocated."""
+        sources = self._sources
+        if net is not None:
+            if net.training:
+                raise ValueError("load_weights: the network is in training mode, call net.eval() first")
+            try:
+                ops, _ = self._trace_ops(net)
+            except AssertionError as e:
+                raise ValueError("load_weights: the network cannot be traced at %s: %s" % (self.input_shape, e))
+            for i, (op, want) in enumerate(zip(ops, self._signature)):
+                got = self._op_signature(op)
+                if got != want:
+                    raise ValueError("load_weights: op %d differs from the network this engine was built for: %r, built for %r" % (i, got, want))
+            if len(ops) != len(self._signature):
+                raise ValueError("load_weights: the network traces to %d ops, this engine was built for %d" % (len(ops), len(self._signature)))
+            sources = ops
+        self._check_sources(sources)
+        first = self._refresh_tab is None
+        self._sources = sources
+        tab = self._refresh_table()
+        if not first and self._bind_sources():
+            tab["dev"].copy_(tab["host"])
+        call("fs_refresh_weights", K._stream(), K._p(tab["dev"]), len(self._refresh), K._p(tab["chunks"]), tab["n_chunks"])
 
     # ---- 4. run ----------------------------------------------------------------------------------------
     def _launch_all(self):

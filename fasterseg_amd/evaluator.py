@@ -71,6 +71,21 @@ class SegEvaluator:
         self.labels = labels                        # visualize.LabelSpec: the colours of the pictures
         self._writer = None
 
+    def load_weights(self, network=None):
+        """The weights changed (train/train.py:196-208: the model being trained is validated after the first and every tenth
+        epoch, search/train_search.py:141-183 after every epoch): every engine this evaluator has built - the class-map engine
+        and the "lowres" engine of each window shape - re-derives its packs and folded BatchNorms with one launch each
+        (InferenceEngine.load_weights) instead of being rebuilt and re-tuned.  network=None: the module given at construction
+        was updated in place; a module: it replaces val_func (same architecture, else ValueError and nothing is written).  The
+        histogram accumulators and the writer are left alone."""
+        if network is not None:
+            network = network.eval()
+        engines = ([self.engine] if self.engine is not None else []) + list(self._lowres.values())
+        for eng in engines:
+            eng.load_weights(network)
+        if network is not None:
+            self.val_func = network
+
     def process_image(self, img):
         """HWC uint8 (numpy or tensor, RGB like the reference after its BGR->RGB flip) -> normalised (1, 3, H, W) fp32 on the
         device: tools/utils/img_utils.py:178-184 normalize + the transpose of evaluator.py:346."""

@@ -48,6 +48,20 @@ class StudentDistillStep:
             self.teacher_engine = InferenceEngine(self.teacher, (batch, 3, height, width), dtype=teacher_engine_dtype,
                                                   output="lowres" if self.fused_loss else "logits")
 
+    def load_teacher(self, state):
+        """A trained teacher after construction (train/train.py:124-135 loads weights0.pt into the model it has just initialised):
+        `state` is a state_dict or a module; only the keys the teacher has are taken (:126-129), the result is broadcast under DP
+        as in the constructor, and the teacher's engine, if there is one, follows with InferenceEngine.load_weights - one launch,
+        no new engine."""
+        if isinstance(state, torch.nn.Module):
+            state = state.state_dict()
+        own = self.teacher.state_dict()
+        own.update({k: v for k, v in state.items() if k in own})
+        self.teacher.load_state_dict(own)
+        broadcast_parameters(self.teacher)
+        if self.teacher_engine is not None:
+            self.teacher_engine.load_weights()
+
     def teacher_logits(self, imgs):
         with torch.no_grad():
             if self.teacher_engine is not None:

@@ -93,7 +93,7 @@ typedef struct fs_resize_desc {
 const char* fs_last_error(void);
 /* ABI revision of this header; fs_version() returns the one the library was built from.  Bindings check both this and
  * fs_struct_size() when they load the library (fasterseg_amd/_lib.py) - a stale .so must not be used silently. */
-#define FS_ABI_VERSION 217
+#define FS_ABI_VERSION 218
 int fs_version(void);
 /* Bit-reproducible mode (default off; FS_DETERMINISTIC=1 in the environment turns it on at load): every cross-block reduction that
  * otherwise uses float atomics - the pixel slabs of fs_conv2d_wgrad_ws, BatchNorm statistics and parameter gradients of maps above
@@ -111,7 +111,7 @@ void fs_set_fp32_split(int on);
 int fs_get_fp32_split(void);
 int fs_struct_size(int which);   /* 0 fs_conv_desc, 1 fs_resize_desc, 2 fs_zoom_desc, 3 fs_sgd_tensor, 4 fs_logits_desc,
                                     5 fs_eval_window_desc, 6 fs_train_sample, 7 fs_train_batch_desc, 8 fs_heads_desc,
-                                    9 fs_render_desc; -1 otherwise */
+                                    9 fs_render_desc, 11 fs_refresh_entry (10 is unassigned); -1 otherwise */
 /* test hook: force the tile configuration of fs_conv2d_fwd (0..7; -1 = heuristic).  Not for production use. */
 void fs_debug_force_conv_cfg(int cfg);
 /* number of elements of a packed filter bank for (Cout,R,S,Cin) */
@@ -402,6 +402,50 @@ fs_status fs_sgd_momentum_multi(void* stream, const fs_sgd_tensor* tensors, cons
                                 const unsigned char* touched, const float* grads, float* momentum_buf,
                                 const float* grad_scale, float lr, float momentum, float weight_decay, int pack_dtype,
                                 int pack_only);
+
+/* --- reload the weight-derived buffers of a built inference engine (ABI 218) ------------------------------------------- */
+/* An inference engine folds every eval-mode BatchNorm into scale / shift, packs every filter bank and bakes the addresses of those
+ * buffers into its launch records and its captured hipGraph.  When the weights change - the model validated after an epoch of training
+ * (train/train.py:196-208, search/train_search.py:141-183), a teacher checkpoint loaded after construction (train/train.py:124-135) -
+ * ONE launch rewrites all of those buffers in place from the current parameters; the plan, the graph and every address stay.
+ * `entries` is a DEVICE array of n_entries entries, one per destination; `chunks` is a DEVICE array of n_chunks (entry index, chunk
+ * index) pairs, one per block, chunk index 0 .. fs_refresh_entry_chunks(entry) - 1 (the shape of fs_sgd_momentum_multi; a pair that
+ * names no entry or no chunk of its entry writes nothing; n_chunks == 0 launches nothing).  Forms:
+ *   FS_REFRESH_PACK       dst = [Cout][R][S][Cin] in `dtype` from the strided OIHW fp32 filter `src` (o_stride / i_stride in elements,
+ *                         contiguous taps): the bytes fs_pack_weight(..., transpose_flip = 0) writes (the fp32 stem pack included)
+ *   FS_REFRESH_PACK_FRAG  dst = the fragment-order bank of a 3x3 filter: the bytes fs_pack_weight_frag writes, zeros outside the bank
+ *                         included (fs_packed_weight_frag_elems(Cout, Cin, dtype) elements)
+ *   FS_REFRESH_FOLD       eval-mode BatchNorm as scale / shift over channels lo .. lo + Cout - 1 of the module (lo > 0: the second half
+ *                         of FactorizedReduce's BatchNorm): dst[c] = src[lo + c] * rsqrtf(var[lo + c] + eps) (src = gamma),
+ *                         shift[c] = beta[lo + c] - mean[lo + c] * dst[c], fp32
+ *   FS_REFRESH_BIAS       shift[c] = src[c] for c < Cout (the classifier's bias), fp32
+ * Nothing is allocated, copied from the host or cleared: the call only enqueues the launch on `stream`, and is capturable.  The
+ * entries live on the device, so the call cannot check them: validate each one with fs_refresh_entry_chunks before uploading it. */
+#define FS_REFRESH_PACK      0
+#define FS_REFRESH_PACK_FRAG 1
+#define FS_REFRESH_FOLD      2
+#define FS_REFRESH_BIAS      3
+typedef struct fs_refresh_entry {
+    int kind;               /* FS_REFRESH_*                                                                     */
+    int dtype;              /* packs: fs_dtype of dst                                                           */
+    int Cout, Cin;          /* packs: filter block packed; fold / bias: Cout = channels written (Cin unused)    */
+    int R, S;               /* packs: taps (3 x 3 for FS_REFRESH_PACK_FRAG)                                     */
+    int lo;                 /* fold: first channel of the BatchNorm module that is read                         */
+    float eps;              /* fold                                                                             */
+    long long o_stride, i_stride;   /* packs: element strides of src per output / input channel               */
+    const float* src;       /* packs: OIHW filter; fold: gamma; bias: the bias vector                           */
+    const float* beta;      /* fold                                                                             */
+    const float* mean;      /* fold: running_mean                                                               */
+    const float* var;       /* fold: running_var                                                                */
+    void* dst;              /* packs: the packed bank; fold: scale; bias: unused                                */
+    float* shift;           /* fold / bias                                                                      */
+} fs_refresh_entry;
+int fs_refresh_chunk_elems(void);
+/* Blocks the refresh kernel needs for `e` (a HOST copy of the entry): ceil(destination elements / fs_refresh_chunk_elems()).
+ * Host only, no device needed.  -1 with a message in fs_last_error for an entry the kernel must not see: unknown kind, Cout or Cin
+ * below 1, taps below 1 or other than 3 x 3 for a fragment pack, a bad dtype, a negative stride or lo, a null source or destination. */
+long long fs_refresh_entry_chunks(const fs_refresh_entry* e);
+fs_status fs_refresh_weights(void* stream, const fs_refresh_entry* entries, int n_entries, const int* chunks, int n_chunks);
 
 /* --- OHEM cross-entropy on NCHW fp32 logits ------------------------- */
 /* Forward pass of ProbOhemCrossEntropy2d (tools/seg_opr/loss_opr.py:63-93) without materialising softmax / log_softmax:
