@@ -281,4 +281,12 @@ __device__ __forceinline__ Tap make_tap(float scale, int dst, int in_size) {
     t.l0 = 1.f - t.l1;
     return t;
 }
+// The bilinear blend of four taps in ONE fixed operation order (explicit fma: no contraction choice is left to the compiler), so
+// equal inputs give equal bits for every class and in every kernel that uses it: an arg-max over classes breaks exact ties by
+// index, and a backward that re-evaluates a forward's logits gets the same logits.
+__device__ __forceinline__ float bilerp(const Tap& th, const Tap& tw, float p00, float p01, float p10, float p11) {
+    const float top = __builtin_fmaf(tw.l1, p01, tw.l0 * p00);
+    const float bot = __builtin_fmaf(tw.l1, p11, tw.l0 * p10);
+    return __builtin_fmaf(th.l1, bot, th.l0 * top);
+}
 }  // namespace fs

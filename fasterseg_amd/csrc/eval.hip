@@ -8,8 +8,9 @@
 //                        (N, Ho, Wo): 2 MB written instead of 159 MB, nothing materialised in between;
 //   fs_hist_info         n_cl x n_cl confusion counts + labeled + correct from (pred, gt) on the device, integer atomics
 //                        (bit-exact with np.bincount).
-// The interpolation uses the same tap arithmetic and expression as bilinear_fwd_nchw_kernel (resize.hip), so the class map
-// equals the arg-max of the logits tensor the engine would have written (first maximum wins, as np.argmax).
+// The interpolation uses the tap arithmetic of bilinear_fwd_nchw_kernel (resize.hip) and blends the taps with common.h's bilerp, whose
+// operation order is fixed: classes with equal taps get equal bits, so an exact tie goes to the lowest class index (np.argmax); the
+// class map equals the arg-max of the logits tensor the engine would have written up to ties in the last bits.
 #include "common.h"
 
 namespace fs {
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(256) void bilinear_argmax_kernel(int N, int Hi, int
                 Quad4<T>::load(r1 + (long long)tw[q].i1 * x_cs + c0, p11);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float v = th.l0 * (tw[q].l0 * p00[k] + tw[q].l1 * p01[k]) + th.l1 * (tw[q].l0 * p10[k] + tw[q].l1 * p11[k]);
+                    const float v = bilerp(th, tw[q], p00[k], p01[k], p10[k], p11[k]);
                     if (c0 + k < C && v > best[q]) {       // strict: the first maximum wins (np.argmax)
                         best[q] = v;
                         arg[q] = c0 + k;
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(256) void bilinear_argmax8_kernel(int N, int Hi, in
                 const float p10 = a1 ? bot[1][c] : bot[0][c];
                 const float p01 = rel1 >= 2 ? top[2][c] : (rel1 == 1 ? top[1][c] : top[0][c]);
                 const float p11 = rel1 >= 2 ? bot[2][c] : (rel1 == 1 ? bot[1][c] : bot[0][c]);
-                const float val = th.l0 * (tw.l0 * p00 + tw.l1 * p01) + th.l1 * (tw.l0 * p10 + tw.l1 * p11);
+                const float val = bilerp(th, tw, p00, p01, p10, p11);
                 if (c < C && val > best) {
                     best = val;
                     arg = c;

@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void heads_confusion8_kernel(HeadsArgs a, int 
                 const float p10 = a1 ? bot[1][c] : bot[0][c];
                 const float p01 = rel1 >= 2 ? top[2][c] : (rel1 == 1 ? top[1][c] : top[0][c]);
                 const float p11 = rel1 >= 2 ? bot[2][c] : (rel1 == 1 ? bot[1][c] : bot[0][c]);
-                const float val = th.l0 * (tw.l0 * p00 + tw.l1 * p01) + th.l1 * (tw.l0 * p10 + tw.l1 * p11);
+                const float val = bilerp(th, tw, p00, p01, p10, p11);
                 if (c < C && val > best) {
                     best = val;
                     arg = c;
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void heads_confusion_kernel(HeadsArgs a, int N
             HQuad<T>::load(r1 + (long long)tw.i1 * cs + c0, p11);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float v = th.l0 * (tw.l0 * p00[j] + tw.l1 * p01[j]) + th.l1 * (tw.l0 * p10[j] + tw.l1 * p11[j]);
+                const float v = bilerp(th, tw, p00[j], p01[j], p10[j], p11[j]);
                 if (c0 + j < C && v > best) {
                     best = v;
                     arg = c0 + j;

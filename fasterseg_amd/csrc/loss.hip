@@ -5,7 +5,7 @@
 // logits are 478 MB per head, and the ATen chain moves that tensor ~10 times (softmax out, transposed copy, log_softmax out,
 // nll, and their backwards).  Here the forward reads the logits once and emits two per-pixel vectors (probability of the
 // true class, log-sum-exp); the hard-example threshold of the unweighted criterion is still found with a device sort of that
-// vector (the class-weighted criterion selects with ohem_select.hip); the backward reads the logits once more and writes
+// vector (the class-weighted criterion selects with ohem_select.hip); the backward reads the logits again, re-derives the softmax and writes
 // d logits = kept * (softmax - onehot) * scale directly (kept: a byte, or fs_ohem_select's per-pixel coefficient).
 #include "common.h"
 
@@ -22,13 +22,13 @@ __global__ __launch_bounds__(256) void ohem_ce_fwd_kernel(const float* __restric
         for (int c = 0; c < C; ++c) m = fmaxf(m, base[(long long)c * HW]);
         float s = 0.f;
         for (int c = 0; c < C; ++c) s += expf(base[(long long)c * HW] - m);
-        const float lse = m + logf(s);
+        const float ls = logf(s);
         const long long t = target[p];
         const bool valid = t != (long long)ignore && t >= 0 && t < C;
-        const float xt = valid ? base[t * HW] : 0.f;
-        true_prob[p] = valid ? expf(xt - lse) : 1.f;            // ignored pixels never count as hard examples
-        nll[p] = valid ? lse - xt : 0.f;
-        lse_out[p] = lse;
+        const float nl = valid ? ls - (base[t * HW] - m) : 0.f;      // (x_t - m) - log s: no rounding at the magnitude of the logits
+        true_prob[p] = valid ? expf(-nl) : 1.f;                 // ignored pixels never count as hard examples
+        nll[p] = nl;
+        lse_out[p] = m + ls;
     }
 }
 
@@ -36,8 +36,7 @@ __global__ __launch_bounds__(256) void ohem_ce_fwd_kernel(const float* __restric
 // pixel's class weight, 0 for a dropped one), which scales the pixel's gradient
 template <typename KT>
 __global__ __launch_bounds__(256) void ohem_ce_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
-                                                          const float* __restrict__ lse, const KT* __restrict__ kept,
-                                                          const float* __restrict__ scale, int C, long long HW, long long P,
+                                                          const KT* __restrict__ kept, const float* __restrict__ scale, int C, long long HW, long long P,
                                                           float* __restrict__ dlogits) {
     constexpr bool COEF = sizeof(KT) == sizeof(float);
     const float g = *scale;
@@ -45,13 +44,22 @@ __global__ __launch_bounds__(256) void ohem_ce_bwd_kernel(const float* __restric
         const long long b = p / HW, hw = p - b * HW;
         const long long off = b * C * HW + hw;
         const KT kv = kept[p];
-        const bool k = kv != 0;
         const float gk = COEF ? g * (float)kv : g;
-        const float l = lse[p];
         const long long t = target[p];
+        const bool k = kv != 0 && t >= 0 && t < C;       // a label outside [0, C) has nll = 0 in the forward: no gradient
+        // softmax as exp((x - max) - log(sum)), re-derived here: the forward's one fp32 lse is rounded at the magnitude of the logits
+        // (half an ulp of 100 is 3.8e-6 of every probability of the pixel); the re-reads of the pixel's C logits hit the cache
+        float m = 0.f, ls = 0.f;
+        if (k) {
+            m = -INFINITY;
+            for (int c = 0; c < C; ++c) m = fmaxf(m, logits[off + (long long)c * HW]);
+            float s = 0.f;
+            for (int c = 0; c < C; ++c) s += expf(logits[off + (long long)c * HW] - m);
+            ls = logf(s);
+        }
         for (int c = 0; c < C; ++c) {
             float d = 0.f;
-            if (k) d = (expf(logits[off + (long long)c * HW] - l) - (c == t ? 1.f : 0.f)) * gk;
+            if (k) d = (expf((logits[off + (long long)c * HW] - m) - ls) - (c == t ? 1.f : 0.f)) * gk;
             __builtin_nontemporal_store(d, dlogits + off + (long long)c * HW);
         }
     }
@@ -76,10 +84,11 @@ __global__ __launch_bounds__(256) void kl_fwd_kernel(const float* __restrict__ s
             ss += expf(s_logits[off + (long long)c * HW] - ms);
             st += expf(t_logits[off + (long long)c * HW] - mt);
         }
-        const float ls = ms + logf(ss), lt = mt + logf(st);
+        const float gs = logf(ss), gt = logf(st);
+        const float ls = ms + gs, lt = mt + gt;
         float acc = 0.f;
-        for (int c = 0; c < C; ++c) {
-            const float lps = s_logits[off + (long long)c * HW] - ls, lpt = t_logits[off + (long long)c * HW] - lt;
+        for (int c = 0; c < C; ++c) {         // (x - m) - log s: no rounding at the magnitude of the logits
+            const float lps = (s_logits[off + (long long)c * HW] - ms) - gs, lpt = (t_logits[off + (long long)c * HW] - mt) - gt;
             const float pt = expf(lpt);
             acc += pt > 0.f ? pt * (lpt - lps) : 0.f;          // xlogy convention of F.kl_div: 0 * log 0 = 0
         }
@@ -90,17 +99,27 @@ __global__ __launch_bounds__(256) void kl_fwd_kernel(const float* __restrict__ s
 }
 
 __global__ __launch_bounds__(256) void kl_bwd_kernel(const float* __restrict__ s_logits, const float* __restrict__ t_logits,
-                                                     const float* __restrict__ lse_s, const float* __restrict__ lse_t,
                                                      const float* __restrict__ scale, int C, long long HW, long long P,
                                                      float* __restrict__ d_s) {
     const float g = *scale;
     for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < P; p += (long long)gridDim.x * blockDim.x) {
         const long long b = p / HW, hw = p - b * HW;
         const long long off = b * C * HW + hw;
-        const float ls = lse_s[p], lt = lse_t[p];
+        // both softmaxes as exp((x - max) - log(sum)), re-derived as in ohem_ce_bwd_kernel (an lse of magnitude |x| is too coarse)
+        float ms = -INFINITY, mt = -INFINITY;
+        for (int c = 0; c < C; ++c) {
+            ms = fmaxf(ms, s_logits[off + (long long)c * HW]);
+            mt = fmaxf(mt, t_logits[off + (long long)c * HW]);
+        }
+        float ss = 0.f, st = 0.f;
+        for (int c = 0; c < C; ++c) {
+            ss += expf(s_logits[off + (long long)c * HW] - ms);
+            st += expf(t_logits[off + (long long)c * HW] - mt);
+        }
+        const float gs = logf(ss), gt = logf(st);
         for (int c = 0; c < C; ++c) {
             const long long i = off + (long long)c * HW;
-            __builtin_nontemporal_store((expf(s_logits[i] - ls) - expf(t_logits[i] - lt)) * g, d_s + i);
+            __builtin_nontemporal_store((expf((s_logits[i] - ms) - gs) - expf((t_logits[i] - mt) - gt)) * g, d_s + i);
         }
     }
 }
@@ -127,7 +146,7 @@ extern "C" fs_status fs_kl_distill_bwd(void* stream, const float* student, const
     const long long P = B * HW;
     long long blocks = (P + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    FS_LAUNCH(kl_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, student, teacher, lse_s, lse_t, scale,
+    FS_LAUNCH(kl_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, student, teacher, scale,
                        C, HW, P, d_student);
     return check_launch("fs_kl_distill_bwd");
 }
@@ -151,7 +170,7 @@ extern "C" fs_status fs_ohem_ce_bwd(void* stream, const float* logits, const lon
     const long long P = B * HW;
     long long blocks = (P + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    FS_LAUNCH((ohem_ce_bwd_kernel<unsigned char>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, target, lse, kept,
+    FS_LAUNCH((ohem_ce_bwd_kernel<unsigned char>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, target, kept,
                        scale, C, HW, P, dlogits);
     return check_launch("fs_ohem_ce_bwd");
 }
@@ -163,7 +182,7 @@ extern "C" fs_status fs_ohem_ce_bwd_coef(void* stream, const float* logits, cons
     const long long P = B * HW;
     long long blocks = (P + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    FS_LAUNCH((ohem_ce_bwd_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, target, lse, coef, scale,
+    FS_LAUNCH((ohem_ce_bwd_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, target, coef, scale,
                        C, HW, P, dlogits);
     return check_launch("fs_ohem_ce_bwd_coef");
 }

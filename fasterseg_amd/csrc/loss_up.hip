@@ -5,7 +5,7 @@
 // (tools/seg_opr/loss_opr.py:63-93) on each and nn.KLDivLoss against the teacher's (equally up-sampled) logits
 // (train/train.py:254-260).  At 12 x 19 x 512 x 1024 every one of those tensors is 478 MB of fp32 that is written once and
 // read two or three times, forward and backward.  These kernels take the LOW-resolution NHWC logits and evaluate the bilinear
-// interpolation (align_corners=True, same tap arithmetic and expression as resize.hip) per full-resolution pixel on the fly:
+// interpolation (align_corners=True, resize.hip's taps, blended by common.h's fixed-order bilerp) per full-resolution pixel on the fly:
 //   *_up_fwd   one lane per full-resolution pixel: 4 taps x C logits from L2 -> lse / nll / p_target (OHEM) or KL (distill);
 //              the only HBM traffic is three floats per pixel out.
 //   *_up_bwd   the transpose of the interpolation, d lo[i,j,c] = sum_p w(p -> i,j) * dL/dlogit_p[c], in two launches without
@@ -43,10 +43,24 @@ struct UpGeom {
     float rh, rw;
 };
 
+// make_tap with its operations kept apart: left to the compiler, `scale * dst - i0` fuses into one fma in one kernel and not in
+// another, the weights of a column of pixels then differ in their last bit between the forward (which writes lse) and the backward
+// (which forms exp(logit - lse)), and at logits of magnitude 100 that bit is 5e-5 of every probability of the column.
+__device__ __forceinline__ Tap up_tap(float scale, int dst, int in_size) {
+#pragma clang fp contract(off)
+    Tap t;
+    const float src = scale * (float)dst;
+    t.i0 = (int)src;
+    t.i1 = t.i0 + ((t.i0 < in_size - 1) ? 1 : 0);
+    t.l1 = src - (float)t.i0;
+    t.l0 = 1.f - t.l1;
+    return t;
+}
+
 // logits of full-resolution pixel (n, Y, X), interpolated from the low-resolution NHWC map (pad lanes of the last quad readable)
 template <typename T>
 __device__ __forceinline__ void interp_logits(const T* __restrict__ lo, const UpGeom& g, int n, int Y, int X, float* out) {
-    const Tap th = make_tap(g.rh, Y, g.h), tw = make_tap(g.rw, X, g.w);
+    const Tap th = up_tap(g.rh, Y, g.h), tw = up_tap(g.rw, X, g.w);
     const T* r0 = lo + ((long long)n * g.h + th.i0) * g.w * g.cs;
     const T* r1 = lo + ((long long)n * g.h + th.i1) * g.w * g.cs;
 #pragma unroll
@@ -59,7 +73,7 @@ __device__ __forceinline__ void interp_logits(const T* __restrict__ lo, const Up
             QuadL<T>::load(r1 + (long long)tw.i1 * g.cs + q * 4, p11);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                out[q * 4 + k] = th.l0 * (tw.l0 * p00[k] + tw.l1 * p01[k]) + th.l1 * (tw.l0 * p10[k] + tw.l1 * p11[k]);
+                out[q * 4 + k] = bilerp(th, tw, p00[k], p01[k], p10[k], p11[k]);
         }
     }
 }
@@ -150,14 +164,19 @@ __device__ __forceinline__ void cell_sweep(float (&S)[16], float sign, int c0, c
             const KT kv = kept[p];
             keep = COEF ? sign * (float)kv : (kv ? sign : 0.f);
         }
-        const int t = OHEM ? (int)target[p] : -1;
-        const Tap th = make_tap(g.rh, Y, g.h), tw = make_tap(g.rw, X, g.w);
+        int t = -1;
+        if (OHEM) {        // a label outside [0, C) has nll = 0 in the forward: no term here, whatever its kept byte says
+            const long long tl = target[p];
+            if (tl >= 0 && tl < g.C) t = (int)tl;
+            else keep = 0.f;
+        }
+        const Tap th = up_tap(g.rh, Y, g.h), tw = up_tap(g.rw, X, g.w);
         float v[4];
         if (UNIFORM) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) v[c] = th.l0 * (tw.l0 * L[0][c] + tw.l1 * L[1][c]) + th.l1 * (tw.l0 * L[2][c] + tw.l1 * L[3][c]);
-        } else {           // same expression as interp_logits, one quad
-            const Tap uh = make_tap(gl.rh, Y, gl.h), uw = make_tap(gl.rw, X, gl.w);
+            for (int c = 0; c < 4; ++c) v[c] = bilerp(th, tw, L[0][c], L[1][c], L[2][c], L[3][c]);
+        } else {           // interp_logits, one quad
+            const Tap uh = up_tap(gl.rh, Y, gl.h), uw = up_tap(gl.rw, X, gl.w);
             const T* r0 = lo + ((long long)n * gl.h + uh.i0) * gl.w * gl.cs + c0;
             const T* r1 = lo + ((long long)n * gl.h + uh.i1) * gl.w * gl.cs + c0;
             float p00[4], p01[4], p10[4], p11[4];
@@ -166,7 +185,7 @@ __device__ __forceinline__ void cell_sweep(float (&S)[16], float sign, int c0, c
             QuadL<T>::load(r1 + (long long)uw.i0 * gl.cs, p10);
             QuadL<T>::load(r1 + (long long)uw.i1 * gl.cs, p11);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) v[c] = uh.l0 * (uw.l0 * p00[c] + uw.l1 * p01[c]) + uh.l1 * (uw.l0 * p10[c] + uw.l1 * p11[c]);
+            for (int c = 0; c < 4; ++c) v[c] = bilerp(uh, uw, p00[c], p01[c], p10[c], p11[c]);
         }
         const float w00 = keep * th.l0 * tw.l0, w01 = keep * th.l0 * tw.l1, w10 = keep * th.l1 * tw.l0, w11 = keep * th.l1 * tw.l1;
 #pragma unroll

@@ -28,7 +28,7 @@ class _OhemCE(torch.autograd.Function):
         true_prob, nll, lse = buf[0], buf[1], buf[2]
         K.call("fs_ohem_ce_fwd", K._stream(), logits.data_ptr(), tgt.data_ptr(), B, C, HW, int(ignore), true_prob.data_ptr(),
                nll.data_ptr(), lse.data_ptr())
-        valid = tgt.ne(ignore)
+        valid = tgt.ne(ignore) & tgt.ge(0) & tgt.lt(C)         # fs_ohem_select's rule: a label outside [0, C) counts as ignored
         num_valid = valid.sum()
         kept = valid
         if min_kept > 0:        # the reference builds kept_mask only inside `if self.min_kept > 0` (loss_opr.py:80-86)
@@ -222,7 +222,7 @@ class _OhemCEUp(torch.autograd.Function):
         true_prob, nll, lse = buf[0], buf[1], buf[2]
         x = pred_lo.detach()
         K.call("fs_ohem_ce_up_fwd", K._stream(), ctypes.byref(d), K._p(x), K._p(tgt), int(ignore), K._p(true_prob), K._p(nll), K._p(lse))
-        valid = tgt.ne(ignore)
+        valid = tgt.ne(ignore) & tgt.ge(0) & tgt.lt(d.C)       # fs_ohem_select's rule: a label outside [0, C) counts as ignored
         num_valid = valid.sum()
         kept = valid
         if min_kept > 0:

@@ -454,7 +454,11 @@ fs_status fs_refresh_weights(void* stream, const fs_refresh_entry* entries, int 
  * threshold from true_prob and reduces nll over the kept pixels. */
 fs_status fs_ohem_ce_fwd(void* stream, const float* logits, const long long* target, long long B, int C, long long HW, int ignore,
                          float* true_prob, float* nll, float* lse);
-/* dlogits[b][c][hw] = kept[p] ? (exp(logit - lse[p]) - [c == target[p]]) * (*scale) : 0   (scale: device scalar) */
+/* dlogits[b][c][hw] = kept[p] ? (exp(logit - lse[p]) - [c == target[p]]) * (*scale) : 0   (scale: device scalar; any non-zero
+ * byte keeps).  A pixel whose label is outside [0, C) has nll = 0 in the forward and gets a zero gradient here whatever kept[p]
+ * holds; the same in fs_ohem_ce_bwd_coef and the two fs_ohem_ce_up_bwd* entry points.  `lse` (and lse_s / lse_t of fs_kl_distill_bwd)
+ * must be the forward's vector but is not read: the softmax is re-derived from the logits as exp((x - max) - log(sum)), because one
+ * fp32 lse is rounded at the magnitude of the logits and that rounding would enter every probability of the pixel. */
 fs_status fs_ohem_ce_bwd(void* stream, const float* logits, const long long* target, const float* lse, const unsigned char* kept,
                          const float* scale, long long B, int C, long long HW, float* dlogits);
 
