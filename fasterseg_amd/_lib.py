@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfasterseg_hip.so")
 
-EXPECTED_ABI = 218          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
+EXPECTED_ABI = 219          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
 FS_F32, FS_BF16 = 0, 1
 FS_CONV_RELU, FS_CONV_TRANSPOSED, FS_CONV_ACCUM, FS_CONV_RELU_TAIL = 1, 2, 4, 8
 FS_CONV_KSPLIT, FS_CONV_NO_KSPLIT, FS_CONV_KSPLIT16 = 0x4000, 0x8000, 0x14000   # fs_conv3x3_s1_fwd: force / forbid the K-split form (16: 16-channel tiles)
@@ -176,6 +176,8 @@ _SPECIAL = {
     "fs_packed_weight_elems": ([c_int, c_int, c_int, c_int], c_ll),
     "fs_debug_force_conv_cfg": ([c_int], None),
     "fs_debug_stem_mfma": ([c_int], None),
+    "fs_debug_stem_blocks": ([c_int], None),
+    "fs_debug_logits_tiled": ([c_int], None),
     "fs_packed_weight_frag_elems": ([c_int, c_int, c_int], c_ll),
     "fs_sgd_chunk_elems": ([], c_int),
     "fs_sgd_tensor_chunks": ([c_ll, c_int, c_int, c_int], c_ll),

@@ -51,6 +51,21 @@ __device__ __forceinline__ void bilinear_fwd_body(const ResizeArgs& q, int bx, i
     }
 }
 
+// make_tap with the product rounded BEFORE the subtraction.  The compiler otherwise contracts scale * dst - i0 into one fma for some
+// taps of a kernel and not for others (its choice, per call site): l1 then differs from ATen's fp32 value by up to half an ulp of src
+// (2^-17 at source column 128..255), far above the rounding of the blend.  The NCHW logits writers below all use this form, so they
+// agree with each other and with the fp32 tap arithmetic of the header comment to the last bit of the weights.
+__device__ __forceinline__ Tap make_tap_rn(float scale, int dst, int in_size) {
+#pragma clang fp contract(off)
+    Tap t;
+    const float src = scale * (float)dst;
+    t.i0 = (int)src;
+    t.i1 = t.i0 + ((t.i0 < in_size - 1) ? 1 : 0);
+    t.l1 = src - (float)t.i0;
+    t.l0 = 1.f - t.l1;
+    return t;
+}
+
 // NHWC (channel stride padded to a multiple of 4, pad lanes readable) -> NCHW.  One lane: 4 consecutive ow x 4 channels.
 // Each tap is ONE vector load of 4 channels (8 B bf16 / 16 B fp32); the low-resolution logits are L2-resident, the
 // kernel is bound by the NCHW write (16-byte stores per channel plane).
@@ -93,13 +108,13 @@ __global__ __launch_bounds__(256) void bilinear_fwd_nchw_kernel(int N, int Hi, i
         const int oh = divmod32(t, Ho);
         const int c0 = divmod32(t, cg) * 4;
         const int n = (int)t;
-        const Tap th = make_tap(rh, oh, Hi);
+        const Tap th = make_tap_rn(rh, oh, Hi);
         const T* r0 = x + ((long long)n * Hi + th.i0) * Wi * x_cs + c0;
         const T* r1 = x + ((long long)n * Hi + th.i1) * Wi * x_cs + c0;
         float out[4][4];   // [channel][q]
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const Tap tw = make_tap(rw, ow0 + q, Wi);
+            const Tap tw = make_tap_rn(rw, ow0 + q, Wi);
             float p00[4], p01[4], p10[4], p11[4];
             Quad<T>::load(r0 + (long long)tw.i0 * x_cs, p00);
             Quad<T>::load(r0 + (long long)tw.i1 * x_cs, p01);
@@ -115,6 +130,80 @@ __global__ __launch_bounds__(256) void bilinear_fwd_nchw_kernel(int N, int Hi, i
     }
 }
 
+// Tiled form of the NCHW writer for up-samples (the x8 logits): the kernel above gathers 16 taps per lane and output row although at
+// x8 the four pixels of a lane span half an input pixel and ~8 output rows share their two source rows - it is bound by its own L1
+// gathers, not by the NCHW write.  Here a block owns an LT_TR x LT_TW output tile of all C channels and
+//   1. stages the source window of the tile (rows i0(first row) .. i1(last row), likewise columns) into LDS ONCE, channel-planar,
+//      converted to fp32 (one 4-channel vector load per pixel and channel group, as above: pad channels are readable);
+//   2. a wave takes (channel, LT_SEG-row segment) items; a lane owns one column quad and walks down the segment's rows, keeping the
+//      horizontal interpolations of the current source row pair in registers (h0 / h1) and re-reading LDS only when i0 changes;
+//   3. every output row is th.l0 * h0 + th.l1 * h1: the expression tree of the kernel above with the same make_tap weights, so
+//      the two differ by FMA contraction only; one 16-byte store per lane, plane and row, a wave's 64 lanes on 1 KB of one plane row.
+// Plain grid, no traffic between workgroups.
+constexpr int LT_TR = 32, LT_TW = 256, LT_SEG = 8;
+constexpr int LT_LDS_BYTES = 64 * 1024;       // budget of the staged window (dynamic LDS); decides the dispatch
+// upper bound of the source rows (columns) under `t` consecutive output rows (columns): i1(last) - i0(first) + 1 <= floor((t-1)*r) + 3,
+// one more for the fp32 rounding of scale * dst
+static inline int lt_span(int t, float r) { return (int)((float)(t - 1) * r) + 4; }
+
+template <typename T, typename TO>
+__global__ __launch_bounds__(256) void bilinear_fwd_nchw_tiled_kernel(int Hi, int Wi, int Ho, int Wo, int C, float rh, float rw,
+                                                                      const T* __restrict__ x, int x_cs, TO* __restrict__ y) {
+    extern __shared__ __attribute__((aligned(16))) float lt_win[];        // [channel][source row][source column]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ow_t = blockIdx.x * LT_TW, oh_t = blockIdx.y * LT_TR, n = blockIdx.z;
+    const int rows = min(LT_TR, Ho - oh_t), cols = min(LT_TW, Wo - ow_t);
+    const int r_lo = make_tap_rn(rh, oh_t, Hi).i0, c_lo = make_tap_rn(rw, ow_t, Wi).i0;
+    const int nr = make_tap_rn(rh, oh_t + rows - 1, Hi).i1 - r_lo + 1, nc = make_tap_rn(rw, ow_t + cols - 1, Wi).i1 - c_lo + 1;
+    const int plane = nr * nc;
+    const int cg = (C + 3) >> 2;
+    const T* src = x + (long long)n * Hi * Wi * x_cs;
+    for (int it = tid; it < cg * plane; it += 256) {          // pixel fastest: a wave writes consecutive words of four planes
+        const int g = it / plane, p = it - g * plane;
+        const int r = p / nc, c = p - r * nc;
+        float v[4];
+        Quad<T>::load(src + ((long long)(r_lo + r) * Wi + c_lo + c) * x_cs + g * 4, v);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) lt_win[(g * 4 + k) * plane + p] = v[k];
+    }
+    __syncthreads();
+    const int ow0 = ow_t + lane * 4;
+    if (ow0 >= Wo) return;
+    Tap tw[4];
+    int o0[4], o1[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        tw[q] = make_tap_rn(rw, ow0 + q, Wi);
+        o0[q] = tw[q].i0 - c_lo;
+        o1[q] = tw[q].i1 - c_lo;
+    }
+    const int nseg = (rows + LT_SEG - 1) / LT_SEG;
+    for (int it = wave; it < C * nseg; it += 4) {
+        const int c = it / nseg, r0 = (it - c * nseg) * LT_SEG, r1 = min(r0 + LT_SEG, rows);
+        const float* pl = lt_win + c * plane;
+        TO* dst = y + (((long long)n * C + c) * Ho + oh_t + r0) * Wo + ow0;
+        int cur = -1;
+        float h0[4] = {0.f, 0.f, 0.f, 0.f}, h1[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int r = r0; r < r1; ++r, dst += Wo) {
+            const Tap th = make_tap_rn(rh, oh_t + r, Hi);
+            if (th.i0 != cur) {                              // wave-uniform: every ~1/rh rows
+                cur = th.i0;
+                const float* a = pl + (th.i0 - r_lo) * nc;
+                const float* b = pl + (th.i1 - r_lo) * nc;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    h0[q] = tw[q].l0 * a[o0[q]] + tw[q].l1 * a[o1[q]];
+                    h1[q] = tw[q].l0 * b[o0[q]] + tw[q].l1 * b[o1[q]];
+                }
+            }
+            float o[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o[q] = th.l0 * h0[q] + th.l1 * h1[q];
+            store4<TO>(dst, o);
+        }
+    }
+}
+
 // generic scalar NCHW writer for Wo % 4 != 0
 template <typename T, typename TO>
 __global__ void bilinear_fwd_nchw_scalar_kernel(int N, int Hi, int Wi, int Ho, int Wo, int C, float rh, float rw,
@@ -127,7 +216,7 @@ __global__ void bilinear_fwd_nchw_scalar_kernel(int N, int Hi, int Wi, int Ho, i
         const int oh = divmod32(t, Ho);
         const int c = divmod32(t, C);
         const int n = (int)t;
-        const Tap th = make_tap(rh, oh, Hi), tw = make_tap(rw, ow, Wi);
+        const Tap th = make_tap_rn(rh, oh, Hi), tw = make_tap_rn(rw, ow, Wi);
         const T* b = x + (long long)n * Hi * Wi * x_cs + c;
         const float p00 = Elem<T>::load(b + ((long long)th.i0 * Wi + tw.i0) * x_cs);
         const float p01 = Elem<T>::load(b + ((long long)th.i0 * Wi + tw.i1) * x_cs);
@@ -368,6 +457,10 @@ static inline int grid_for(long long work, int block = 256, int cap = 16384) {
 
 using namespace fs;
 
+static int g_logits_tiled = 1;
+/* test hook: 0 = the NCHW up-sample always takes the gather kernel (bilinear_fwd_nchw_kernel), never the tiled form */
+extern "C" void fs_debug_logits_tiled(int on) { g_logits_tiled = on; }
+
 static fs_status check_resize(const char* fn, const fs_resize_desc* d) {
     FS_REQUIRE(d, FS_ERR_INVALID, "%s: null descriptor", fn);
     FS_REQUIRE(d->N > 0 && d->Hi > 0 && d->Wi > 0 && d->Ho > 0 && d->Wo > 0 && d->C > 0, FS_ERR_INVALID,
@@ -402,7 +495,23 @@ extern "C" fs_status fs_bilinear_fwd(void* stream, const fs_resize_desc* d, cons
         else FS_LAUNCH((bilinear_fwd_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, st, q);
     } else {
         const bool out_f32 = (d->out_nchw == 1) || d->dtype == FS_F32;
-        if (d->Wo % 4 == 0) {
+        // tiled form: the staged window of a tile must fit its LDS budget (any up-sample by ~x4 or more at 19 classes; a down-sample or a
+        // ratio near 1 does not - the bound is that of the ratio, not clamped to the map) and the grid its y / z limits
+        const long long lt_bytes = (long long)((d->C + 3) / 4) * 16 * lt_span(LT_TR, rh) * lt_span(LT_TW, rw);
+        if (d->Wo % 4 == 0 && g_logits_tiled && lt_bytes <= LT_LDS_BYTES && d->N <= 65535 && d->Ho <= 65535 * LT_TR && d->Hi < 32768 &&
+            d->Wi < 32768) {
+            const dim3 g((unsigned)((d->Wo + LT_TW - 1) / LT_TW), (unsigned)((d->Ho + LT_TR - 1) / LT_TR), (unsigned)d->N);
+            const size_t lds = (size_t)lt_bytes;
+            if (d->dtype == FS_F32)
+                FS_LAUNCH((bilinear_fwd_nchw_tiled_kernel<float, float>), g, dim3(256), lds, st, d->Hi, d->Wi, d->Ho, d->Wo, d->C, rh, rw,
+                                   (const float*)x, d->x_cs, (float*)y);
+            else if (out_f32)
+                FS_LAUNCH((bilinear_fwd_nchw_tiled_kernel<bf16_t, float>), g, dim3(256), lds, st, d->Hi, d->Wi, d->Ho, d->Wo, d->C, rh, rw,
+                                   (const bf16_t*)x, d->x_cs, (float*)y);
+            else
+                FS_LAUNCH((bilinear_fwd_nchw_tiled_kernel<bf16_t, bf16_t>), g, dim3(256), lds, st, d->Hi, d->Wi, d->Ho, d->Wo, d->C, rh,
+                                   rw, (const bf16_t*)x, d->x_cs, (bf16_t*)y);
+        } else if (d->Wo % 4 == 0) {
             const long long total = (long long)d->N * ((d->C + 3) / 4) * d->Ho * (d->Wo / 4);
             const dim3 g(grid_for(total));
             if (d->dtype == FS_F32)

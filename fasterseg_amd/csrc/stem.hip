@@ -166,105 +166,163 @@ __device__ __forceinline__ void split_bf16(const float (&v)[8], u32x4& hi, u32x4
     }
 }
 
-__global__ __launch_bounds__(256) void stem_mfma_kernel(int H, int W, int Ho, int Wo, int Cout, const float* __restrict__ x,
-                                                        const float* __restrict__ w, const float* __restrict__ scale,
-                                                        const float* __restrict__ shift, bf16_t* __restrict__ y, int y_cs, int relu) {
-    constexpr int WIN = 2 * 3 * S_ROWS * S_PITCH;            // floats: [parity][c][row][col]
-    constexpr int OUT_PITCH = 32 * 2 + 16;                   // bytes per pixel row of the transpose tile
-    __shared__ __attribute__((aligned(16))) float win[WIN + 4];          // + a zero word for the K padding
-    __shared__ __attribute__((aligned(16))) unsigned char sout[4][32 * OUT_PITCH];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-    const int ow0 = blockIdx.x * S_TW, oh0 = blockIdx.y * S_TH, n = blockIdx.z;
-    constexpr int VPR = S_HALF / 2;
-    for (int v = tid; v < 3 * S_ROWS * VPR; v += 256) {
-        const int c = v / (S_ROWS * VPR);
-        const int rem = v - c * (S_ROWS * VPR);
-        const int r = rem / VPR, q = rem - r * VPR;
+// Multi-tile, software-pipelined form.  One 4 x 64 tile per block left a CU with four short serial chains (image loads -> LDS ->
+// barrier -> gathers -> MFMA -> transpose -> stores) and every block re-gathered and re-split the same filter.  Now
+//   * the grid is at most `4 blocks per compute unit`; block b walks tiles b, b + gridDim.x, ... of a linear order that runs down the
+//     rows (ty fastest, then tx, then n) in a plain bounded loop: no tile counter in memory, nothing shared between blocks;
+//   * the filter fragments (bh / bl) are loaded and split ONCE per block, before the loop;
+//   * the window is double-buffered: the NEXT tile's image loads are issued into registers before the current tile's LDS gathers and
+//     MFMAs and written into the other window buffer after them - one __syncthreads() per tile.
+// The arithmetic per output is the single-tile kernel's (same operand split, the same three MFMAs per kk in the same order, scale /
+// shift / ReLU, one bf16 rounding): outputs are bit-identical to it (tests/test_stem_pipelined_gpu.py, tests/golden/stem_parent.npz).
+constexpr int S_VPR = S_HALF / 2;                          // float4 vectors per staged row (33)
+constexpr int S_VECS = 3 * S_ROWS * S_VPR;                 // float4 vectors of a tile's window (891)
+constexpr int S_LD = (S_VECS + 255) / 256;                 // ... per thread (4)
+constexpr int S_WIN = 2 * 3 * S_ROWS * S_PITCH;            // floats of a window: [parity][c][row][col]
+
+__device__ __forceinline__ void stem_tile_origin(int t, int tyn, int txn, int& n, int& oh0, int& ow0) {
+    const int u = t / tyn;
+    n = u / txn;
+    oh0 = (t - u * tyn) * S_TH;
+    ow0 = (u - n * txn) * S_TW;
+}
+
+__device__ __forceinline__ void stem_load_window(f32x4 (&reg)[S_LD], const float* __restrict__ x, int H, int W, int n, int oh0, int ow0,
+                                                 int tid) {
+#pragma unroll
+    for (int j = 0; j < S_LD; ++j) {
+        const int v = tid + 256 * j;
+        const int c = v / (S_ROWS * S_VPR);
+        const int rem = v - c * (S_ROWS * S_VPR);
+        const int r = rem / S_VPR, q = rem - r * S_VPR;
         const int ih = 2 * oh0 - 1 + r, iw = 2 * ow0 - 4 + 4 * q;
         f32x4 t = {0.f, 0.f, 0.f, 0.f};
-        if ((unsigned)ih < (unsigned)H && iw >= 0 && iw + 3 < W)
+        if (v < S_VECS && (unsigned)ih < (unsigned)H && iw >= 0 && iw + 3 < W)
             t = *reinterpret_cast<const f32x4*>(x + (((long long)n * 3 + c) * H + ih) * W + iw);
-        float* ev = win + ((0 * 3 + c) * S_ROWS + r) * S_PITCH;
-        float* od = win + ((1 * 3 + c) * S_ROWS + r) * S_PITCH;
-        ev[2 * q] = t[0]; od[2 * q] = t[1];
-        ev[2 * q + 1] = t[2]; od[2 * q + 1] = t[3];
+        reg[j] = t;
     }
-    if (tid < 4) win[WIN + tid] = 0.f;
-    // filter fragments of this lane: B[k][n = l31], k = kk*16 + half*8 + e, split like the image
-    const int ntiles = (Cout + 31) / 32;
-    u32x4 bh[2][2], bl[2][2];                                 // [n-tile (<= 2: Cout <= 64)][kk]
+}
+
+__device__ __forceinline__ void stem_write_window(const f32x4 (&reg)[S_LD], float* win, int tid) {
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+    for (int j = 0; j < S_LD; ++j) {
+        const int v = tid + 256 * j;
+        if (v < S_VECS) {
+            const int c = v / (S_ROWS * S_VPR);
+            const int rem = v - c * (S_ROWS * S_VPR);
+            const int r = rem / S_VPR, q = rem - r * S_VPR;
+            float* ev = win + ((0 * 3 + c) * S_ROWS + r) * S_PITCH;
+            float* od = win + ((1 * 3 + c) * S_ROWS + r) * S_PITCH;
+            ev[2 * q] = reg[j][0]; od[2 * q] = reg[j][1];
+            ev[2 * q + 1] = reg[j][2]; od[2 * q + 1] = reg[j][3];
+        }
+    }
+}
+
+template <int NT>                                            // n-tiles of 32 output channels: 1 (Cout <= 32) or 2
+__global__ __launch_bounds__(256, NT == 1 ? 4 : 3) void stem_mfma_kernel(int N, int H, int W, int Ho, int Wo, int Cout, const float* __restrict__ x,
+                                                        const float* __restrict__ w, const float* __restrict__ scale,
+                                                        const float* __restrict__ shift, bf16_t* __restrict__ y, int y_cs, int relu) {
+    constexpr int OUT_PITCH = 32 * 2 + 16;                   // bytes per pixel row of the transpose tile
+    __shared__ __attribute__((aligned(16))) float win[2][S_WIN + 4];     // two window buffers, each + a zero word for the K padding
+    __shared__ __attribute__((aligned(16))) unsigned char sout[4][32 * OUT_PITCH];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
+    const int txn = (Wo + S_TW - 1) / S_TW, tyn = (Ho + S_TH - 1) / S_TH;
+    const int total = N * txn * tyn;
+    int t = blockIdx.x;
+    if (t >= total) return;
+    int n, oh0, ow0;
+    f32x4 reg[S_LD];
+    stem_tile_origin(t, tyn, txn, n, oh0, ow0);
+    stem_load_window(reg, x, H, W, n, oh0, ow0, tid);
+    if (tid < 4) win[0][S_WIN + tid] = 0.f;
+    else if (tid < 8) win[1][S_WIN + tid - 4] = 0.f;
+    // filter fragments of this lane: B[k][n = l31], k = kk*16 + half*8 + e, split like the image - once per block
+    u32x4 bh[NT][2], bl[NT][2];                               // [n-tile][kk]
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             float wv[8];
-            const int co = t * 32 + l31;
+            const int co = nt * 32 + l31;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int k = kk * 16 + half * 8 + e;
-                wv[e] = (t < ntiles && co < Cout && k < 27) ? w[co * 27 + k] : 0.f;
+                wv[e] = (co < Cout && k < 27) ? w[co * 27 + k] : 0.f;
             }
-            split_bf16(wv, bh[t][kk], bl[t][kk]);
+            split_bf16(wv, bh[nt][kk], bl[nt][kk]);
         }
+    stem_write_window(reg, win[0], tid);
     __syncthreads();
     // wave = output row `wave` of the tile; m-tile h = columns [32h, 32h + 32)
     const int ty = wave;
-    const int oh = oh0 + ty;
     unsigned char* so = sout[wave];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int tx = 32 * h + l31;
-        const float* base = win + (2 * ty) * S_PITCH + tx;
-        u32x4 ah[2], al[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            float av[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                constexpr int dummy = 0;
-                (void)dummy;
-                const int o0 = stem_tap_offset(kk * 16 + e), o1 = stem_tap_offset(kk * 16 + 8 + e);
-                const float* p0 = o0 >= 0 ? base + o0 : win + WIN;
-                const float* p1 = o1 >= 0 ? base + o1 : win + WIN;
-                av[e] = *(half ? p1 : p0);
-            }
-            split_bf16(av, ah[kk], al[kk]);
+    for (int buf = 0;; buf ^= 1) {
+        const int tn = t + (int)gridDim.x;
+        const bool more = tn < total;                         // block-uniform
+        int nn = 0, noh0 = 0, now0 = 0;
+        if (more) {                                           // the next tile's image loads fly during this tile's gathers and MFMAs
+            stem_tile_origin(tn, tyn, txn, nn, noh0, now0);
+            stem_load_window(reg, x, H, W, nn, noh0, now0, tid);
         }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            if (t >= ntiles) break;
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        const float* wb = win[buf];
+        const int oh = oh0 + ty;
+#pragma unroll 1                                              // not unrolled: both m-tiles' 64 gathered taps at once spill
+        for (int h = 0; h < 2; ++h) {
+            const int tx = 32 * h + l31;
+            const float* base = wb + (2 * ty) * S_PITCH + tx;
+            u32x4 ah[2], al[2];
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[kk]), __builtin_bit_cast(bf16x8, bh[t][kk]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[kk]), __builtin_bit_cast(bf16x8, bl[t][kk]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[kk]), __builtin_bit_cast(bf16x8, bh[t][kk]), acc, 0, 0, 0);
-            }
-            const int co = t * 32 + l31;
-            const bool cvalid = co < Cout;
-            const float sc = (scale && cvalid) ? scale[co] : 1.f, sh = (shift && cvalid) ? shift[co] : 0.f;
+                float av[8];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int prow = (r & 3) + 8 * (r >> 2) + 4 * half;               // pixel (column) of the m-tile
-                float o = acc[r] * sc + sh;
-                if (relu) o = fmaxf(o, 0.f);
-                *reinterpret_cast<bf16_t*>(so + prow * OUT_PITCH + l31 * 2) = f32_to_bf16(o);
+                for (int e = 0; e < 8; ++e) {
+                    const int o0 = stem_tap_offset(kk * 16 + e), o1 = stem_tap_offset(kk * 16 + 8 + e);
+                    const float* p0 = o0 >= 0 ? base + o0 : wb + S_WIN;
+                    const float* p1 = o1 >= 0 ? base + o1 : wb + S_WIN;
+                    av[e] = *(half ? p1 : p0);
+                }
+                split_bf16(av, ah[kk], al[kk]);
             }
-            __builtin_amdgcn_wave_barrier();
-            const int cbase = t * 32;
-            const int nvalid = Cout - cbase < 32 ? Cout - cbase : 32;                // multiple of 8 (y_cs and Cout are)
 #pragma unroll
-            for (int ps = 0; ps < 2; ++ps) {                                      // 32 pixels x 4 vectors of 8 channels
-                const int prow = ps * 16 + (lane >> 2), seg = lane & 3;
-                const int ow = ow0 + 32 * h + prow;
-                if (oh < Ho && ow < Wo && seg * 8 < nvalid)
-                    stg16(y + (((long long)n * Ho + oh) * Wo + ow) * y_cs + cbase + seg * 8,
-                          *reinterpret_cast<const u32x4*>(so + prow * OUT_PITCH + seg * 16));
+            for (int nt = 0; nt < NT; ++nt) {
+                f32x16 acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[kk]), __builtin_bit_cast(bf16x8, bh[nt][kk]), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[kk]), __builtin_bit_cast(bf16x8, bl[nt][kk]), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[kk]), __builtin_bit_cast(bf16x8, bh[nt][kk]), acc, 0, 0, 0);
+                }
+                const int co = nt * 32 + l31;
+                const bool cvalid = co < Cout;
+                const float sc = (scale && cvalid) ? scale[co] : 1.f, sh = (shift && cvalid) ? shift[co] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int prow = (r & 3) + 8 * (r >> 2) + 4 * half;               // pixel (column) of the m-tile
+                    float o = acc[r] * sc + sh;
+                    if (relu) o = fmaxf(o, 0.f);
+                    *reinterpret_cast<bf16_t*>(so + prow * OUT_PITCH + l31 * 2) = f32_to_bf16(o);
+                }
+                __builtin_amdgcn_wave_barrier();
+                const int cbase = nt * 32;
+                const int nvalid = Cout - cbase < 32 ? Cout - cbase : 32;                // multiple of 8 (y_cs and Cout are)
+#pragma unroll
+                for (int ps = 0; ps < 2; ++ps) {                                      // 32 pixels x 4 vectors of 8 channels
+                    const int prow = ps * 16 + (lane >> 2), seg = lane & 3;
+                    const int ow = ow0 + 32 * h + prow;
+                    if (oh < Ho && ow < Wo && seg * 8 < nvalid)
+                        stg16(y + (((long long)n * Ho + oh) * Wo + ow) * y_cs + cbase + seg * 8,
+                              *reinterpret_cast<const u32x4*>(so + prow * OUT_PITCH + seg * 16));
+                }
+                __builtin_amdgcn_wave_barrier();
             }
-            __builtin_amdgcn_wave_barrier();
         }
+        if (!more) break;
+        stem_write_window(reg, win[buf ^ 1], tid);
+        __syncthreads();                                      // the other buffer is complete; every wave is done reading this one
+        t = tn; n = nn; oh0 = noh0; ow0 = now0;
     }
 }
 
@@ -275,6 +333,18 @@ using namespace fs;
 static int g_stem_mfma = 1;
 /* test hook: 0 = always the direct (vector-ALU) stem kernel */
 extern "C" void fs_debug_stem_mfma(int on) { g_stem_mfma = on; }
+static int g_stem_blocks = 0;
+static int compute_units() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+        else cus = 256;
+    }
+    return cus;
+}
+/* test hook: 0 = default grid, n > 0 = at most n blocks (every block walks many tiles) */
+extern "C" void fs_debug_stem_blocks(int n) { g_stem_blocks = n; }
 
 extern "C" fs_status fs_conv_stem_fwd(void* stream, int N, int H, int W, int Cout, const float* x, const float* w,
                                       const float* scale, const float* shift, void* y, int y_cs, int dtype, int relu) {
@@ -286,9 +356,17 @@ extern "C" fs_status fs_conv_stem_fwd(void* stream, int N, int H, int W, int Cou
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     if (W % 4 == 0 && aligned16(x) && N <= 65535) {          // LDS-tiled kernels: coalesced 16-byte image loads
         dim3 tiles((unsigned)((Wo + S_TW - 1) / S_TW), (unsigned)((Ho + S_TH - 1) / S_TH), (unsigned)N);
-        if (dtype == FS_BF16 && Cout <= 64 && Cout % 8 == 0 && g_stem_mfma) {      // matrix-core form (split-bf16 operands)
-            FS_LAUNCH(stem_mfma_kernel, tiles, dim3(256), 0, (hipStream_t)stream, H, W, Ho, Wo, Cout, x, w, scale, shift,
-                               (bf16_t*)y, y_cs, relu);
+        const long long ntile = (long long)tiles.x * tiles.y * tiles.z;
+        if (dtype == FS_BF16 && Cout <= 64 && Cout % 8 == 0 && g_stem_mfma && ntile < (1ll << 31)) {      // matrix-core form (split-bf16 operands)
+            // resident blocks per compute unit: 4 x 39.6 KB of LDS at one n-tile; two n-tiles hold twice the filter fragments (3 by registers)
+            long long blocks = g_stem_blocks > 0 ? g_stem_blocks : (long long)(Cout <= 32 ? 4 : 3) * compute_units();
+            if (blocks > ntile) blocks = ntile;
+            if (Cout <= 32)
+                FS_LAUNCH(stem_mfma_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, N, H, W, Ho, Wo, Cout, x, w,
+                                   scale, shift, (bf16_t*)y, y_cs, relu);
+            else
+                FS_LAUNCH(stem_mfma_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, N, H, W, Ho, Wo, Cout, x, w,
+                                   scale, shift, (bf16_t*)y, y_cs, relu);
             return check_launch("fs_conv_stem_fwd");
         }
         if (dtype == FS_F32)

@@ -93,7 +93,7 @@ typedef struct fs_resize_desc {
 const char* fs_last_error(void);
 /* ABI revision of this header; fs_version() returns the one the library was built from.  Bindings check both this and
  * fs_struct_size() when they load the library (fasterseg_amd/_lib.py) - a stale .so must not be used silently. */
-#define FS_ABI_VERSION 218
+#define FS_ABI_VERSION 219
 int fs_version(void);
 /* Bit-reproducible mode (default off; FS_DETERMINISTIC=1 in the environment turns it on at load): every cross-block reduction that
  * otherwise uses float atomics - the pixel slabs of fs_conv2d_wgrad_ws, BatchNorm statistics and parameter gradients of maps above
@@ -224,11 +224,17 @@ fs_status fs_conv_stem_fwd(void* stream, int N, int H, int W, int Cout, const fl
 
 /* test hook: 0 = fs_conv_stem_fwd always takes the direct vector-ALU kernel, 1 (default) = bf16 outputs take the MFMA form */
 void fs_debug_stem_mfma(int on);
+/* test hook (ABI 219): 0 (default) = the MFMA stem's grid is min(tiles, 4 blocks per compute unit); n > 0 caps it at n blocks, so that
+   every block walks many 4 x 64 tiles of a small image */
+void fs_debug_stem_blocks(int n);
 
 /* --- bilinear resize, align_corners=True -------------------------------------------------------- */
 /* Replaces F.interpolate(mode='bilinear', align_corners=True) (operations.py:271,275,437,444;
  * model_seg.py:305,310,317,359-365; model_search.py:339-357). */
 fs_status fs_bilinear_fwd(void* stream, const fs_resize_desc* d, const void* x, void* y);
+/* test hook (ABI 219): 0 = an NCHW output always takes the gather kernel, 1 (default) = up-samples whose source window fits the LDS
+   budget of a tile take the tiled form */
+void fs_debug_logits_tiled(int on);
 /* backward: dx (+)= transpose-of-interpolation(dy); relu mask taken from y_out when d->relu. dx is zeroed by the
  * kernel's gather formulation (no atomics). `y_out` may be NULL when relu==0. */
 fs_status fs_bilinear_bwd(void* stream, const fs_resize_desc* d, const void* dy, const void* y_out, void* dx);

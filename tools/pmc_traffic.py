@@ -19,7 +19,7 @@ import sys
 
 FRAMES = 10
 FAMILY = [("zoom_cell_kernel", "zoomcell"), ("conv3x3_halo_kernel", "conv"), ("conv_igemm_kernel", "conv"), ("stem_", "stem"),
-          ("bilinear_fwd_nchw_kernel", "resize_nchw"), ("bilinear_argmax", "resize_argmax"), ("bilinear_fwd_kernel", "resize")]
+          ("bilinear_fwd_nchw_kernel", "resize_nchw"), ("bilinear_fwd_nchw_tiled_kernel", "resize_nchw"), ("bilinear_argmax", "resize_argmax"), ("bilinear_fwd_kernel", "resize")]
 
 
 def family(name):
