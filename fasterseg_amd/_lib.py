@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfasterseg_hip.so")
 
-EXPECTED_ABI = 219          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
+EXPECTED_ABI = 220          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
 FS_F32, FS_BF16 = 0, 1
 FS_CONV_RELU, FS_CONV_TRANSPOSED, FS_CONV_ACCUM, FS_CONV_RELU_TAIL = 1, 2, 4, 8
 FS_CONV_KSPLIT, FS_CONV_NO_KSPLIT, FS_CONV_KSPLIT16 = 0x4000, 0x8000, 0x14000   # fs_conv3x3_s1_fwd: force / forbid the K-split form (16: 16-channel tiles)
@@ -26,6 +26,13 @@ class ConvDesc(ctypes.Structure):
 
 class ZoomDesc(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("N", "H", "W", "Cin", "Cmid", "Cout", "h", "w", "Ho", "Wo", "x_cs", "y_cs", "dtype", "down", "up")]
+
+
+class ConvPwDesc(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("N", "H", "W", "Cin", "C3", "Cout", "x_cs", "y_cs", "dtype", "flags")]
+
+
+FS_PW_RELU_3X3, FS_PW_RELU_POST, FS_PW_ROWS4, FS_PW_ROWS8 = 8, 16, 0x100, 0x200
 
 
 class LogitsDesc(ctypes.Structure):
@@ -100,6 +107,8 @@ SIGNATURES = {
     "fs_pack_weight_frag": [c_vp, c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp],
     "fs_conv3x3_s1_fwd": [c_vp, ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "fs_conv3x3_halo_plan": [ctypes.POINTER(ConvDesc), c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_ll)],
+    "fs_conv3x3_pw_fwd": [c_vp, ctypes.POINTER(ConvPwDesc)] + [c_vp] * 8,
+    "fs_conv3x3_pw_plan": [ctypes.POINTER(ConvPwDesc), c_vp, c_vp, c_vp],
     "fs_zoom_cell_fwd": [c_vp, ctypes.POINTER(ZoomDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "fs_conv_stem_fwd": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int],
     "fs_bilinear_fwd": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp],
@@ -231,7 +240,7 @@ def lib():
             raise ImportError("libfasterseg_hip.so has ABI %d, these bindings expect %d: rebuild with `python -m fasterseg_amd.build "
                               "--force`" % (got, EXPECTED_ABI))
         for which, struct in list(enumerate((ConvDesc, ResizeDesc, ZoomDesc, SgdTensor, LogitsDesc, EvalWindowDesc,
-                                                TrainSample, TrainBatchDesc, HeadsDesc, RenderDesc))) + [(11, RefreshEntry)]:
+                                                TrainSample, TrainBatchDesc, HeadsDesc, RenderDesc))) + [(11, RefreshEntry), (13, ConvPwDesc)]:
             if handle.fs_struct_size(which) != ctypes.sizeof(struct):
                 raise ImportError("libfasterseg_hip.so: sizeof(%s) is %d in the library, %d in the bindings - stale build" % (
                     struct.__name__, handle.fs_struct_size(which), ctypes.sizeof(struct)))

@@ -44,6 +44,7 @@ extern "C" int fs_struct_size(int which) {
         case 8: return (int)sizeof(fs_heads_desc);
         case 9: return (int)sizeof(fs_render_desc);
         case 11: return (int)sizeof(fs_refresh_entry);      // 10 stays unassigned (-1)
+        case 13: return (int)sizeof(fs_conv_pw_desc);           // 12 stays unassigned (-1)
         default: return -1;
     }
 }

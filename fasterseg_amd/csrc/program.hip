@@ -225,6 +225,10 @@ fs_status st = FS_OK;
             NEED(9);
             st = fs_zoom_cell_fwd(stream, (const fs_zoom_desc*)P(0), P(1), P(2), PF(3), PF(4), P(5), PF(6), PF(7), P(8));
             break;
+        case FS_OP_CONV3X3_PW:
+            NEED(9);
+            st = fs_conv3x3_pw_fwd(stream, (const fs_conv_pw_desc*)P(0), P(1), P(2), PF(3), PF(4), P(5), PF(6), PF(7), P(8));
+            break;
         case FS_OP_STEM:
             NEED(12);
             st = fs_conv_stem_fwd(stream, I(0), I(1), I(2), I(3), PF(4), PF(5), PF(6), PF(7), P(8), I(9), I(10), I(11));

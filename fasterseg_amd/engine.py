@@ -99,7 +99,13 @@ class InferenceEngine:
         # written to <file>.<output> after a build that timed them and read back by later builds instead of timing (a plan
         # tuned on an idle device can be replayed under a profiler, whose counters perturb the timings it would otherwise tune on)
         self._plan_path = os.environ.get("FS_ENGINE_PLAN")
-        self._plan_in, self._plan_out = None, {"convs": [], "cells": [], "folds": []}
+        self._plan_in, self._plan_out = None, {"convs": [], "cells": [], "folds": [], "heads": []}
+        self._plan_heads = None
+        # a 1x1 conv behind a 3x3 / stride-1 conv whose map nothing else reads (heads.conv_3x3 -> heads.conv_1x1, an arm's 3x3 -> 1x1)
+        # as ONE launch (conv3x3_pw.hip): 0 never, 1 (default) where the whole
+        # frame gets faster, 2 always where the geometry is supported
+        self.fuse_head = int(os.environ.get("FS_ENGINE_FUSE_HEAD", "1"))
+        self.head_log = []
         # a 1/2 (or x2) resample whose only reader is a 3x3 / stride-1 conv can be folded into that conv's LDS-halo staging
         # (fs_conv_desc.vr_* on fs_conv3x3_s1_fwd): "auto" (default) = per resample, whichever is faster in the frame; 0 never; 1 always
         self.fold_resizes = os.environ.get("FS_ENGINE_FOLD_RESIZE", "auto")
@@ -118,21 +124,32 @@ class InferenceEngine:
                     plan = json.load(f)
                 if plan.get("signature") == sig and "folds" in plan:
                     self._plan_in = plan
+                    self._plan_heads = plan.get("heads")     # a plan written before the head fusion existed: only the heads are tuned
         self._fuse_cells()
         self._fuse_resizes()
         self._mark_halo_folds()
+        self._mark_head_fusions()
         self._assign_buffers()
         self._lower()
         self.graph = None
+        heads_untuned = self._plan_heads is None and any(len(g["variants"]) > 1 and g["kind"] == "head" for g in self.groups)
         if use_graph:
             if self._plan_in is None and any(len(g["variants"]) > 1 for g in self.groups):
                 self._warm()
                 self._tune_cells()
+            elif heads_untuned:
+                self._warm()
+                self._tune_cells(kinds=("head",))
             self._capture()
-        if self._plan_path and self._plan_in is None:
+        heads_untuned = heads_untuned and use_graph          # without a graph nothing was timed: the plan file stays as it is
+        if self._plan_path and (self._plan_in is None or heads_untuned):
             import json
-            self._plan_out["cells"] = [g["choice"] for g in self.groups if len(g["variants"]) > 1 and g["kind"] == "zoom"]
-            self._plan_out["folds"] = [g["choice"] for g in self.groups if len(g["variants"]) > 1 and g["kind"] != "zoom"]
+            if self._plan_in is not None:
+                self._plan_out.update({k: self._plan_in[k] for k in ("convs", "cells", "folds")})
+            else:
+                self._plan_out["cells"] = [g["choice"] for g in self.groups if len(g["variants"]) > 1 and g["kind"] == "zoom"]
+                self._plan_out["folds"] = [g["choice"] for g in self.groups if len(g["variants"]) > 1 and g["kind"] not in ("zoom", "head")]
+            self._plan_out["heads"] = [[g["choice"], g["rows"]] for g in self.groups if g["kind"] == "head"]
             with open(self._plan_path, "w") as f:
                 json.dump(self._plan_out, f)
 
@@ -333,6 +350,18 @@ class InferenceEngine:
                     and cop["x"] is rop["out"]):
                 cop["fold"] = rop
                 self.halo_folds += 1
+
+    # ---- 1d. 1x1 convs around a 3x3 / stride-1 conv whose intermediate maps have one reader --------------------------------
+    def _mark_head_fusions(self):
+        """`3x3 -> 1x1` chains whose intermediate map has exactly one consumer and is not the engine's output (head_fusion.match).
+        Candidates only: `_lower` builds the fused launch (fs_conv3x3_pw_fwd) beside the separate
+        launches and `_tune_cells` keeps it where the frame gets faster.  bf16 only: the fp32 engine keeps the separate launches."""
+        from . import head_fusion
+        self.head_matches = []
+        if getattr(self, "fuse_head", 1) and getattr(self, "dtype", torch.bfloat16) == torch.bfloat16:
+            self.head_matches = head_fusion.match(self.ops, self.out_sym)
+        for m in self.head_matches:
+            self.ops[m["post"]]["head"] = m
 
     # ---- 2. buffers: one NHWC buffer per feature map; cat operands alias slices of the cat buffer ------
     def _new_buffer(self, N, H, W, cs, zero=False):
@@ -705,7 +734,77 @@ class InferenceEngine:
             if alt is not None:
                 group.update(alt)
             self.groups.append(group)
+            if op.get("head") is not None:
+                self._add_head(op["head"])
         self._flatten()
+
+    _HEAD_NAMES = ("split", "fused")
+
+    def _add_head(self, m):
+        """The groups just lowered for the 3x3 conv and the 1x1 conv of a head match become ONE group whose variants are the separate
+        launches (the parent's list, variant 0) and the fused launch.  The fused launch reads the members' own packed filters, scales
+        and shifts (the 3x3's fragment pack is made here when that layer runs on the implicit GEMM), so `load_weights` reaches it
+        through the members' records.  Rows per block (4 / 8): whichever is faster alone."""
+        C = self.ops[m["conv"]]
+        gis = []
+        for o in (C, self.ops[m["post"]]):
+            gi = next((i for i, g in enumerate(self.groups) if g["out"] is o["out"]), None)
+            if gi is None or len(self.groups[gi]["variants"]) != 1 or len(self.groups[gi]["variants"][0]) != 1:
+                return
+            gis.append(gi)
+        cc, cq = (self.groups[gi]["variants"][0][0] for gi in gis)
+        dq = cq["desc"]
+        if not (cq["fn"] == "fs_conv2d_fwd" and dq.R == 1 and dq.S == 1 and dq.stride == 1 and dq.pad == 0 and dq.vr_H == 0 and dq.w_os == 0):
+            return
+        if cc["fn"] == "fs_conv3x3_s1_fwd":
+            wf_ptr = cc["args"][2]
+        else:
+            wf = K.pack_weight_frag(C["weight"].detach().to(self.device), self.dtype, C["cout"], C["cin"])
+            self._keep.append(wf)
+            self._record(_lib.FS_REFRESH_PACK_FRAG, C["weight"], wf, cout=C["cout"], cin=C["cin"], dtype=self.dtype)
+            wf_ptr = ctypes.c_void_p(wf.data_ptr())
+        es = 2
+        dc = cc["desc"]
+        N, H, W = dc.N, dc.H, dc.W
+
+        def fused(rows):
+            d = K.conv_pw_desc((N, dc.Cin, H, W), dc.x_cs, dc.Cout, dq.Cout, dq.y_cs, self.dtype, bool(dc.flags & FS_CONV_RELU),
+                               bool(dq.flags & FS_CONV_RELU), rows)
+            if _lib.lib().fs_conv3x3_pw_plan(ctypes.byref(d), None, None, None) != 0:
+                return None
+            self._keep.append(d)
+            args = (ctypes.byref(d), cc["args"][1], wf_ptr, cc["args"][3], cc["args"][4], cq["args"][2], cq["args"][3], cq["args"][4], cq["args"][5])
+            # the 3x3's output map no longer exists: neither its write nor its read
+            return dict(fn="fs_conv3x3_pw_fwd", args=args, desc=d, family="conv3x3", flops=cc["flops"] + cq["flops"],
+                        bytes=cc["bytes"] + cq["bytes"] - 2 * es * N * H * W * dc.Cout,
+                        label="head 3x3+1x1 %d->%d->%d @%dx%d rows%d" % (dc.Cin, dc.Cout, dq.Cout, H, W, rows))
+
+        cands = {r: fused(r) for r in (4, 8)}
+        if any(c is None for c in cands.values()):
+            return
+        planned = None
+        if self._plan_heads is not None and len(self.head_log) < len(self._plan_heads):
+            planned = self._plan_heads[len(self.head_log)]
+        if planned is not None and planned[1] in cands:
+            rows, t = planned[1], None
+        else:
+            timed = {r: self._time_calls([c]) for r, c in cands.items()}
+            rows = min(timed, key=lambda r: (timed[r], r))
+            t = round(timed[rows] * 1e3, 2)
+        variants, names = [[cc, cq], [cands[rows]]], list(self._HEAD_NAMES)
+        if self.fuse_head >= 2:          # forced: the fused launch is the only variant
+            variants, names, choice = variants[1:], names[1:], 0
+        elif planned is not None and int(planned[0]) < len(variants):
+            choice = int(planned[0])
+        else:
+            choice = 0                   # the separate launches, until `_tune_cells` finds the frame faster with the fused one
+        log = ["head %d->%d->%d @%dx%d" % (dc.Cin, dc.Cout, dq.Cout, H, W), names[choice], t]
+        self.head_log.append(log)
+        group = dict(kind="head", in_syms=self.groups[gis[0]]["in_syms"], out=self.groups[gis[1]]["out"], variants=variants, choice=choice,
+                     log=log, names=names, rows=rows)
+        for gi in sorted(gis, reverse=True):
+            del self.groups[gi]
+        self.groups.append(group)
 
     def _add_fold(self, op, out, scale, shift, first_call):
         """The conv just lowered (self.calls[first_call:]) reads a resample that nothing else reads: the alternative is ONE halo launch
@@ -742,7 +841,7 @@ class InferenceEngine:
         for g in self.groups:
             deps = sorted({d for s_ in g["in_syms"] for d in self._ready(s_)})
             first = len(self.calls)
-            chain = g["kind"] in ("zoom", "conv") and len(g["variants"][g["choice"]]) > 1     # un-fused cell / un-folded resample: a dependent chain of launches
+            chain = g["kind"] in ("zoom", "conv", "head") and len(g["variants"][g["choice"]]) > 1     # un-fused cell / un-folded resample / un-fused head: a dependent chain of launches
             for k, c in enumerate(g["variants"][g["choice"]]):
                 c = dict(c)
                 c["deps"] = [first + k - 1] if (chain and k > 0) else deps
@@ -756,11 +855,11 @@ class InferenceEngine:
         self.total_flops = sum(c["flops"] for c in self.calls)
         self.total_bytes = sum(c["bytes"] for c in self.calls)
 
-    def _tune_cells(self):
+    def _tune_cells(self, kinds=None):
         """Fused or separate launches, per cell (and, per resample in front of a halo 3x3 conv, folded or materialised), decided on the time of the WHOLE frame (single-stream hipGraph): timed alone,
         back to back, a launch finds its filter bank and input in L2, which flatters the fused kernel (it waits on memory in
         several dependent phases).  Greedy: flip one cell at a time, keep the flip if the frame gets faster."""
-        cells = [g for g in self.groups if len(g["variants"]) > 1]
+        cells = [g for g in self.groups if len(g["variants"]) > 1 and (kinds is None or g["kind"] in kinds)]
         if not cells:
             return
 
@@ -779,7 +878,7 @@ class InferenceEngine:
                     best, keep = t, alt
                 g["log"].append((alt, round(t, 4)))
             g["choice"] = keep
-            g["log"][1] = self._VARIANT_NAMES[keep]
+            g["log"][1] = g.get("names", self._VARIANT_NAMES)[keep]
         self._flatten()
 
 
@@ -1022,7 +1121,7 @@ class InferenceEngine:
             main.wait_event(ev)
 
     # ---- 4b. the plan as one multi-stream launch program (fs_exec_program_streams) ---------------------------------
-    _OPS = {"fs_bilinear_argmax": "OP_BILINEAR_ARGMAX", "fs_zoom_cell_fwd": "OP_ZOOM_CELL", "fs_conv2d_fwd_ws": "OP_CONV_FWD", "fs_conv2d_fwd": "OP_CONV_FWD", "fs_conv3x3_s1_fwd": "OP_CONV3X3_S1",
+    _OPS = {"fs_bilinear_argmax": "OP_BILINEAR_ARGMAX", "fs_zoom_cell_fwd": "OP_ZOOM_CELL", "fs_conv2d_fwd_ws": "OP_CONV_FWD", "fs_conv2d_fwd": "OP_CONV_FWD", "fs_conv3x3_s1_fwd": "OP_CONV3X3_S1", "fs_conv3x3_pw_fwd": "OP_CONV3X3_PW",
             "fs_conv_stem_fwd": "OP_STEM", "fs_bilinear_fwd": "OP_BILINEAR_FWD", "fs_copy_channels": "OP_COPY_CHANNELS"}
 
     def _build_program(self):

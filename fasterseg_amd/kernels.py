@@ -284,6 +284,35 @@ def conv3x3_halo_plan(d, has_stats=False):
     return tile.value, ks.value, wg.value
 
 
+def conv_pw_desc(x_shape, x_cs, c3, cout, y_cs, dtype, relu=False, relu_post=False, rows=0):
+    """fs_conv_pw_desc of a 3x3 / stride-1 conv (-> c3 channels) with a 1x1 conv (-> cout) behind it; rows = 4 / 8 pins the rows per block."""
+    N, Cin, H, W = x_shape
+    flags = (_lib.FS_PW_RELU_3X3 if relu else 0) | (_lib.FS_PW_RELU_POST if relu_post else 0) | {0: 0, 4: _lib.FS_PW_ROWS4, 8: _lib.FS_PW_ROWS8}[rows]
+    return _lib.ConvPwDesc(N, H, W, Cin, c3, cout, x_cs, y_cs, dtype_code(dtype), flags)
+
+
+def conv3x3_pw_plan(d):
+    """(rows per block, workgroups, LDS bytes per block) of the launch fs_conv3x3_pw_fwd makes for `d` (host only, no device needed)."""
+    rows, wg, lds = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_int()
+    call("fs_conv3x3_pw_plan", ctypes.byref(d), ctypes.byref(rows), ctypes.byref(wg), ctypes.byref(lds))
+    return rows.value, wg.value, lds.value
+
+
+def conv3x3_pw(x, w_frag, c3, scale, shift, relu, w_post, cout, scale_post=None, shift_post=None, relu_post=False, out=None, rows=0):
+    """3x3 / stride 1 / pad 1 conv -> 1x1 conv in one launch (conv3x3_pw.hip) with the arithmetic of the separate launches.  w_frag: the
+    fragment pack of the 3x3, w_post: the dense fs_pack_weight bank of the 1x1; `out` may be a channel slice of a wider NHWC buffer."""
+    x_cs = require_nhwc(x, "x")
+    N, Cin, H, W = x.shape
+    if out is None:
+        out = empty_nhwc(N, cout, H, W, x.dtype, x.device)
+    else:
+        assert tuple(out.shape) == (N, cout, H, W) and out.dtype == x.dtype, (tuple(out.shape), (N, cout, H, W))
+    d = conv_pw_desc(x.shape, x_cs, c3, cout, channel_stride(out), x.dtype, relu, relu_post, rows)
+    call("fs_conv3x3_pw_fwd", _stream(), ctypes.byref(d), _p(x), _p(w_frag), _p(scale), _p(shift), _p(w_post), _p(scale_post), _p(shift_post),
+         _p(out))
+    return out
+
+
 def zoom_desc(x_shape, x_cs, cmid, cout, down, up, y_cs, dtype):
     N, Cin, H, W = x_shape
     h, w = (H // 2, W // 2) if down else (H, W)

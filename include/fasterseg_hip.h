@@ -93,7 +93,7 @@ typedef struct fs_resize_desc {
 const char* fs_last_error(void);
 /* ABI revision of this header; fs_version() returns the one the library was built from.  Bindings check both this and
  * fs_struct_size() when they load the library (fasterseg_amd/_lib.py) - a stale .so must not be used silently. */
-#define FS_ABI_VERSION 219
+#define FS_ABI_VERSION 220
 int fs_version(void);
 /* Bit-reproducible mode (default off; FS_DETERMINISTIC=1 in the environment turns it on at load): every cross-block reduction that
  * otherwise uses float atomics - the pixel slabs of fs_conv2d_wgrad_ws, BatchNorm statistics and parameter gradients of maps above
@@ -111,7 +111,7 @@ void fs_set_fp32_split(int on);
 int fs_get_fp32_split(void);
 int fs_struct_size(int which);   /* 0 fs_conv_desc, 1 fs_resize_desc, 2 fs_zoom_desc, 3 fs_sgd_tensor, 4 fs_logits_desc,
                                     5 fs_eval_window_desc, 6 fs_train_sample, 7 fs_train_batch_desc, 8 fs_heads_desc,
-                                    9 fs_render_desc, 11 fs_refresh_entry (10 is unassigned); -1 otherwise */
+                                    9 fs_render_desc, 11 fs_refresh_entry, 13 fs_conv_pw_desc (10 and 12 are unassigned); -1 otherwise */
 /* test hook: force the tile configuration of fs_conv2d_fwd (0..7; -1 = heuristic).  Not for production use. */
 void fs_debug_force_conv_cfg(int cfg);
 /* number of elements of a packed filter bank for (Cout,R,S,Cin) */
@@ -177,6 +177,32 @@ fs_status fs_conv3x3_s1_fwd(void* stream, const fs_conv_desc* d, const void* x, 
  * workgroups launched.  FS_CONV_TILE_* / FS_CONV_KSPLIT / FS_CONV_NO_KSPLIT in d->flags pin the choice; FS_CONV_KSPLIT with
  * has_stats or stride 2 is FS_ERR_UNSUPPORTED, here and in fs_conv3x3_s1_fwd.  Any output pointer may be NULL. */
 fs_status fs_conv3x3_halo_plan(const fs_conv_desc* d, int has_stats, int* tile, int* ksplit, long long* workgroups);
+
+/* 3x3 / stride 1 / pad 1 LDS-halo convolution and the pointwise (1x1) convolution behind it in ONE launch (conv3x3_pw.hip, ABI 220;
+ * inference epilogues, bf16: an fp32 descriptor is FS_ERR_UNSUPPORTED and the caller keeps the separate launches):
+ *   x (N,H,W,Cin) -3x3 * scale + shift, ReLU if FS_PW_RELU_3X3-> C3 -1x1 * scale_post + shift_post, ReLU if FS_PW_RELU_POST-> y (N,H,W,Cout)
+ * i.e. heads.conv_3x3 -> heads.conv_1x1 (model_seg.py:345; seg_oprs.py:22,245) or an arm's 3x3 whose only reader is a 1x1
+ * (model_seg.py:322-334), with the arithmetic of the separate launches: the 3x3's result is rounded to the storage type where the
+ * stand-alone launch stores it.  w_frag is the fragment pack of fs_pack_weight_frag, w_post the dense [Cout][1][1][C3] pack of
+ * fs_pack_weight; scales and shifts may be NULL (identity / zero).  A block owns all C3 channels of 4 x 16 or 8 x 16 pixels: C3 <= 128
+ * (a multiple of 8), Cout <= 128.  Channels Cout .. y_cs of a wider pixel stride are not written; an output slice that is not 16-byte
+ * aligned takes element stores.  fs_conv3x3_pw_plan (host only) gives the rows per block (FS_PW_ROWS4 / FS_PW_ROWS8 pin them;
+ * otherwise 8 where that still launches 256 blocks, else 4), the workgroups and the LDS bytes per block. */
+#define FS_PW_RELU_3X3   8
+#define FS_PW_RELU_POST  16
+#define FS_PW_ROWS4      0x100
+#define FS_PW_ROWS8      0x200
+#define FS_PW_ROWS_MASK  0x300
+typedef struct fs_conv_pw_desc {
+    int N, H, W, Cin;       /* input map                                                        */
+    int C3, Cout;           /* 3x3: Cin -> C3, 1x1: C3 -> Cout                                  */
+    int x_cs, y_cs;         /* channel strides of x and y                                       */
+    int dtype;
+    int flags;              /* FS_PW_*                                                          */
+} fs_conv_pw_desc;
+fs_status fs_conv3x3_pw_plan(const fs_conv_pw_desc* d, int* rows, long long* workgroups, int* lds_bytes);
+fs_status fs_conv3x3_pw_fwd(void* stream, const fs_conv_pw_desc* d, const void* x, const void* w_frag, const float* scale,
+                            const float* shift, const void* w_post, const float* scale_post, const float* shift_post, void* y);
 
 /* One launch for a whole zoomed-conv cell in inference form (zoom_cell.hip):
  *   x (N,H,W,Cin) -[bilinear 1/2 if down]-> (h,w) -conv3x3 * scale1 + shift1, ReLU-> Cmid -conv3x3 * scale2 + shift2-> Cout
@@ -637,6 +663,7 @@ enum {
     FS_OP_BILINEAR_ARGMAX,   /* fs_bilinear_argmax */
     FS_OP_BN_UNIT_FWD,       /* fs_bn_act_train_fwd */
     FS_OP_BN_UNIT_BWD,       /* fs_bn_act_train_bwd */
+    FS_OP_CONV3X3_PW,        /* fs_conv3x3_pw_fwd (ABI 220) */
     FS_OP_COUNT
 };
 

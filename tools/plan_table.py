@@ -2,7 +2,7 @@
 
     python tools/plan_table.py OUT.json [bf16|fp32]
 
-Writes {"frame_ms", "rows": [{label, family, fn, us}], "autotuned", "cells", "folds", "capture_log"}; prints one line per launch."""
+Writes {"frame_ms", "rows": [{label, family, fn, us}], "autotuned", "cells", "folds", "heads", "capture_log"}; prints one line per launch."""
 import json
 import os
 import sys
@@ -32,7 +32,7 @@ def main():
     print("serial sum %.1f us, %d launches" % (sum(t["us"] for t in table), len(table)))
     with open(out, "w") as f:
         json.dump(dict(serial_us=round(sum(t["us"] for t in table), 1), rows=table, autotuned=eng.autotuned, cells=eng.cell_log,
-                       folds=getattr(eng, "fold_log", []), capture_log=getattr(eng, "capture_log", [])), f, indent=1)
+                       folds=getattr(eng, "fold_log", []), heads=getattr(eng, "head_log", []), capture_log=getattr(eng, "capture_log", [])), f, indent=1)
 
 
 if __name__ == "__main__":
