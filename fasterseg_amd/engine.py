@@ -68,8 +68,22 @@ class _Tracer:
 
 class InferenceEngine:
     def __init__(self, net, input_shape, dtype=torch.bfloat16, logits_dtype=torch.float32, device="cuda", use_graph=True,
-                 halo_min_pixels=16384, lanes=3, fuse_cells=None, output="logits"):
+                 halo_min_pixels=16384, lanes=3, fuse_cells=None, output="logits", input="float", image_mean=None, image_std=None):
         assert not net.training, "call net.eval() first"
+        # "float": `self.input` is the normalised fp32 NCHW image; "uint8": it is the uint8 (N, H, W, 3) RGB frame and the stem normalises
+        # while it stages the image (fs_conv_stem_u8_fwd: ((float)u / 255 - image_mean[c]) / image_std[c])
+        if input not in ("float", "uint8"):
+            raise ValueError("input must be 'float' or 'uint8', got %r" % (input,))
+        self.input_mode = input
+        self.image_mean = self.image_std = None
+        if input == "uint8":
+            if image_mean is None or image_std is None:
+                raise ValueError("input='uint8' needs image_mean and image_std (three floats each)")
+            self.image_mean, self.image_std = tuple(float(v) for v in image_mean), tuple(float(v) for v in image_std)
+            if len(self.image_mean) != 3 or len(self.image_std) != 3 or any(v == 0.0 for v in self.image_std):
+                raise ValueError("image_mean / image_std: three values each, std non-zero")
+            if len(input_shape) != 4 or input_shape[1] != 3:
+                raise ValueError("input='uint8' needs input_shape (N, 3, H, W), got %r" % (tuple(input_shape),))
         self.dtype = dtype
         self.device = torch.device(device)
         self.input_shape = tuple(input_shape)
@@ -89,7 +103,11 @@ class InferenceEngine:
         self.autotune = bool(int(os.environ.get("FS_ENGINE_AUTOTUNE", "1")))
         self.autotuned = []
         self.n_lanes = max(1, int(os.environ.get("FS_ENGINE_LANES", lanes)))
-        self.input = torch.zeros(self.input_shape, dtype=torch.float32, device=self.device)
+        if self.input_mode == "uint8":
+            n_, _, h_, w_ = self.input_shape
+            self.input = torch.zeros((n_, h_, w_, 3), dtype=torch.uint8, device=self.device)
+        else:
+            self.input = torch.zeros(self.input_shape, dtype=torch.float32, device=self.device)
         self._keep = []            # tensors referenced by raw pointers in the plan
         # whole zoomed-conv cells (resize -> conv -> conv -> resize) as ONE launch (zoom_cell.hip): 0 off, 1 always when
         # the geometry is supported, "auto" (default) = time the fused launch against the separate launches per cell at build
@@ -680,9 +698,14 @@ class InferenceEngine:
                 args = (N, H, W, cout, ctypes.c_void_p(self.input.data_ptr()), ctypes.c_void_p(wp.data_ptr()), K._p(scale), K._p(shift),
                         ctypes.c_void_p(yp), y_cs, K.dtype_code(self.dtype), int(op["relu"]))
                 Ho, Wo = out.shape[2], out.shape[3]
-                self.calls.append(dict(fn="fs_conv_stem_fwd", args=args, family="stem", flops=2.0 * N * Ho * Wo * cout * 27,
-                                       bytes=4 * N * 3 * H * W + es * N * Ho * Wo * cout,
-                                       label="stem 3x3 s2 3->%d @%dx%d" % (cout, H, W)))
+                if self.input_mode == "uint8":           # the same launch on the uint8 frame: 3 bytes per pixel in, normalised in the stem
+                    self.calls.append(dict(fn="fs_conv_stem_u8_fwd", args=args + self.image_mean + self.image_std, family="stem",
+                                           flops=2.0 * N * Ho * Wo * cout * 27, bytes=N * H * W * 3 + es * N * Ho * Wo * cout,
+                                           label="stem u8 3x3 s2 3->%d @%dx%d" % (cout, H, W)))
+                else:
+                    self.calls.append(dict(fn="fs_conv_stem_fwd", args=args, family="stem", flops=2.0 * N * Ho * Wo * cout * 27,
+                                           bytes=4 * N * 3 * H * W + es * N * Ho * Wo * cout,
+                                           label="stem 3x3 s2 3->%d @%dx%d" % (cout, H, W)))
             elif kind == "conv":
                 scale, shift = self._fold(op["bn"], op["bias"], op["cout"])
                 self._add_conv(op["x"], out, op["weight"], scale, shift, op["k"], op["stride"], op["pad"], op["relu"], op["cout"],
@@ -1122,7 +1145,7 @@ class InferenceEngine:
 
     # ---- 4b. the plan as one multi-stream launch program (fs_exec_program_streams) ---------------------------------
     _OPS = {"fs_bilinear_argmax": "OP_BILINEAR_ARGMAX", "fs_zoom_cell_fwd": "OP_ZOOM_CELL", "fs_conv2d_fwd_ws": "OP_CONV_FWD", "fs_conv2d_fwd": "OP_CONV_FWD", "fs_conv3x3_s1_fwd": "OP_CONV3X3_S1", "fs_conv3x3_pw_fwd": "OP_CONV3X3_PW",
-            "fs_conv_stem_fwd": "OP_STEM", "fs_bilinear_fwd": "OP_BILINEAR_FWD", "fs_copy_channels": "OP_COPY_CHANNELS"}
+            "fs_conv_stem_fwd": "OP_STEM", "fs_conv_stem_u8_fwd": "OP_STEM_U8", "fs_bilinear_fwd": "OP_BILINEAR_FWD", "fs_copy_channels": "OP_COPY_CHANNELS"}
 
     def _build_program(self):
         """Same launches, lanes and cross-lane edges as `_launch_all_lanes`, as a relocatable-free command list (all
@@ -1293,6 +1316,21 @@ class InferenceEngine:
         return self.output
 
     def __call__(self, x):
+        """input="float": x is anything `self.input.copy_` takes (the normalised NCHW image).  input="uint8": x is a uint8 (N, H, W, 3) or
+        (H, W, 3) RGB frame, tensor or array; anything else is a ValueError before a launch."""
+        if self.input_mode == "uint8":
+            if not isinstance(x, torch.Tensor):
+                import numpy as np
+                x = np.asarray(x)
+                if x.dtype != np.uint8:
+                    raise ValueError("uint8 engine: frame dtype is %s, not uint8" % x.dtype)
+                x = torch.from_numpy(np.ascontiguousarray(x))
+            if x.dtype != torch.uint8:
+                raise ValueError("uint8 engine: frame dtype is %s, not torch.uint8" % x.dtype)
+            if x.dim() == 3:
+                x = x.unsqueeze(0)
+            if tuple(x.shape) != tuple(self.input.shape):
+                raise ValueError("uint8 engine: frame shape %s, expected (N, H, W, 3) = %s" % (tuple(x.shape), tuple(self.input.shape)))
         self.input.copy_(x)
         return self.run()
 

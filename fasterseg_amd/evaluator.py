@@ -39,7 +39,7 @@ class _ImageState:
 class SegEvaluator:
     def __init__(self, network, class_num, image_mean, image_std, image_shape=(1024, 2048), dtype=torch.bfloat16, device="cuda",
                  multi_scales=(1,), is_flip=False, crop_size=None, stride_rate=5 / 6, save_path=None, show_image=False,
-                 show_prediction=False, labels=None):
+                 show_prediction=False, labels=None, uint8_input=False):
         self.class_num = class_num
         self.device = torch.device(device)
         self.image_mean = torch.tensor(np.asarray(image_mean, dtype=np.float32), device=self.device).view(1, 3, 1, 1)
@@ -57,9 +57,14 @@ class SegEvaluator:
         assert len(self.multi_scales) == 1 or crop_size is not None, "multi-scale evaluation slides a crop_size window (eval_crop_size)"
         self.val_func = network.eval()
         # the whole-image class-map engine of today's single-scale, no-flip path; built up front when that is the configured path
+        # uint8_input: that path hands the uint8 HWC frame to an engine whose stem normalises it (InferenceEngine(input="uint8")) - no
+        # process_image, no fp32 image; the flip, padded and multi-scale paths resample and keep fs_eval_window_input
+        self.uint8_input = bool(uint8_input)
+        self._u8_engines = {}                       # (H, W) -> uint8 "classes" engine
         self.engine = None
         if len(self.multi_scales) == 1 and not self.is_flip:
-            self.engine = engine.InferenceEngine(self.val_func, (1, 3, H, W), dtype=dtype, output="classes")
+            self.engine = self._u8_engine(H, W) if self.uint8_input else \
+                engine.InferenceEngine(self.val_func, (1, 3, H, W), dtype=dtype, output="classes")
         self.acc = HistAccumulator(class_num, self.device)
         self.cs = K.round_up(class_num, 4)          # fp32 canvas / total channel stride (19 -> 20)
         self._lowres = {}                           # input shape -> "lowres" engine
@@ -81,6 +86,7 @@ class SegEvaluator:
         if network is not None:
             network = network.eval()
         engines = ([self.engine] if self.engine is not None else []) + list(self._lowres.values())
+        engines += [e for e in self._u8_engines.values() if e is not self.engine]
         for eng in engines:
             eng.load_weights(network)
         if network is not None:
@@ -98,6 +104,13 @@ class SegEvaluator:
         if self.engine is None:
             self.engine = engine.InferenceEngine(self.val_func, (1, 3) + tuple(input_data.shape[2:]), dtype=self.dtype, output="classes")
         return self.engine(input_data)[0]
+
+    def _u8_engine(self, H, W):
+        eng = self._u8_engines.get((H, W))
+        if eng is None:
+            eng = self._u8_engines[(H, W)] = engine.InferenceEngine(self.val_func, (1, 3, H, W), dtype=self.dtype, output="classes",
+                                                                    input="uint8", image_mean=self._mean, image_std=self._std)
+        return eng
 
     # ---- device buffers and engines of the multi-scale / flip paths ------------------------------------------------------
     def _lowres_engine(self, shape):
@@ -151,6 +164,10 @@ class SegEvaluator:
         is padded with 0 to it (margins as pad_image_to_shape) and the score cropped back; output_size: the exp-score is
         resized to it (cv2 INTER_LINEAR) before the arg-max.  Returns the uint8 class map on the device."""
         if output_size is None and input_size is None and not self.is_flip:
+            if self.uint8_input:
+                img, _ = self._upload(img)
+                self.engine = self._u8_engine(int(img.shape[0]), int(img.shape[1]))
+                return self.engine(img)[0]
             return self.val_func_process(self.process_image(img))
         img, st = self._upload(img)
         H, W = int(img.shape[0]), int(img.shape[1])

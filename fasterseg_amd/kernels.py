@@ -378,6 +378,19 @@ def conv_stem(x_nchw, w_packed, cout, scale, shift, relu, dtype, out=None):
     return out
 
 
+def conv_stem_u8(img_nhwc, w_packed, cout, scale, shift, relu, dtype, mean, std, out=None):
+    """fs_conv_stem_u8_fwd: the stem on a uint8 (N, H, W, 3) RGB frame, normalised as ((float)u / 255 - mean[c]) / std[c] while it is
+    staged.  The frame may start at any byte (a slice of a larger buffer); W % 4 == 0 and a 4-byte aligned start take the tiled kernels."""
+    N, H, W, C = img_nhwc.shape
+    assert C == 3 and img_nhwc.dtype == torch.uint8 and img_nhwc.is_contiguous()
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if out is None:
+        out = empty_nhwc(N, cout, Ho, Wo, dtype, img_nhwc.device)
+    call("fs_conv_stem_u8_fwd", _stream(), N, H, W, cout, _p(img_nhwc), _p(w_packed), _p(scale), _p(shift), _p(out),
+         channel_stride(out), dtype_code(dtype), int(relu), *([float(v) for v in mean] + [float(v) for v in std]))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------
 # bilinear (align_corners=True)
 # ---------------------------------------------------------------------------------------------------

@@ -164,7 +164,7 @@ class PredictionWriter:
 class SegTester(SegEvaluator):
     """train/test.py SegTester: per frame `<fn>.png`, the prediction as a single-channel PNG of label ids, and with show_prediction
     `<fn>.viz.png`, the image painted by the prediction (RGB), under save_dir.  labels: a visualize.LabelSpec.  evaluator_kwargs go
-    to SegEvaluator (image_shape, dtype, multi_scales, is_flip, crop_size, stride_rate); slots / workers size the writer;
+    to SegEvaluator (image_shape, dtype, multi_scales, is_flip, crop_size, stride_rate, uint8_input); slots / workers size the writer;
     write=False renders every frame but writes no file (timing)."""
 
     def __init__(self, network, class_num, image_mean, image_std, labels, save_dir, show_prediction=False, slots=4, workers=4,

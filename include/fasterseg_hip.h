@@ -93,7 +93,7 @@ typedef struct fs_resize_desc {
 const char* fs_last_error(void);
 /* ABI revision of this header; fs_version() returns the one the library was built from.  Bindings check both this and
  * fs_struct_size() when they load the library (fasterseg_amd/_lib.py) - a stale .so must not be used silently. */
-#define FS_ABI_VERSION 220
+#define FS_ABI_VERSION 221
 int fs_version(void);
 /* Bit-reproducible mode (default off; FS_DETERMINISTIC=1 in the environment turns it on at load): every cross-block reduction that
  * otherwise uses float atomics - the pixel slabs of fs_conv2d_wgrad_ws, BatchNorm statistics and parameter gradients of maps above
@@ -247,6 +247,15 @@ fs_status fs_conv2d_wgrad_ws(void* stream, const fs_conv_desc* d, const void* x,
  * scale/shift/ReLU.  w_packed is [Cout][3][3][3] fp32. */
 fs_status fs_conv_stem_fwd(void* stream, int N, int H, int W, int Cout, const float* x_nchw, const float* w_packed,
                            const float* scale, const float* shift, void* y, int y_cs, int dtype, int relu);
+
+/* The same convolution on a uint8 frame (ABI 221): img is N x H x W x 3, channel-interleaved RGB, contiguous.  Byte u of channel c
+ * enters the convolution as ((float)u / 255.f - mean[c]) / std[c] (fp32, IEEE division); taps outside the image are 0.0 after
+ * normalisation.  For the same normalised values the output equals fs_conv_stem_fwd's bit for bit (same kernels, another loader).
+ * W % 4 == 0 with a 4-byte aligned img takes the LDS-tiled kernels, anything else the direct one.  A zero std is FS_ERR_INVALID.
+ * Both test hooks below steer it as they steer fs_conv_stem_fwd. */
+fs_status fs_conv_stem_u8_fwd(void* stream, int N, int H, int W, int Cout, const unsigned char* img, const float* w_packed,
+                              const float* scale, const float* shift, void* y, int y_cs, int dtype, int relu,
+                              float mean_r, float mean_g, float mean_b, float std_r, float std_g, float std_b);
 
 /* test hook: 0 = fs_conv_stem_fwd always takes the direct vector-ALU kernel, 1 (default) = bf16 outputs take the MFMA form */
 void fs_debug_stem_mfma(int on);
@@ -664,6 +673,7 @@ enum {
     FS_OP_BN_UNIT_FWD,       /* fs_bn_act_train_fwd */
     FS_OP_BN_UNIT_BWD,       /* fs_bn_act_train_bwd */
     FS_OP_CONV3X3_PW,        /* fs_conv3x3_pw_fwd (ABI 220) */
+    FS_OP_STEM_U8,           /* fs_conv_stem_u8_fwd (ABI 221) */
     FS_OP_COUNT
 };
 
