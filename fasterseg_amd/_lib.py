@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfasterseg_hip.so")
 
 EXPECTED_ABI = 221          # FS_ABI_VERSION of include/fasterseg_hip.h these bindings were written against
-FS_F32, FS_BF16 = 0, 1
+FS_F32, FS_BF16, FS_F16 = 0, 1, 2
 FS_CONV_RELU, FS_CONV_TRANSPOSED, FS_CONV_ACCUM, FS_CONV_RELU_TAIL = 1, 2, 4, 8
 FS_CONV_KSPLIT, FS_CONV_NO_KSPLIT, FS_CONV_KSPLIT16 = 0x4000, 0x8000, 0x14000   # fs_conv3x3_s1_fwd: force / forbid the K-split form (16: 16-channel tiles)
 
@@ -112,6 +112,7 @@ SIGNATURES = {
     "fs_zoom_cell_fwd": [c_vp, ctypes.POINTER(ZoomDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "fs_conv_stem_fwd": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int],
     "fs_conv_stem_u8_fwd": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int] + [c_float] * 6,
+    "fs_conv_stem_u8_infer_fwd": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int] + [c_float] * 6,
     "fs_bilinear_fwd": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp],
     "fs_bilinear_argmax": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp],
     "fs_hist_info": [c_vp, c_vp, c_vp, c_int, c_ll, c_int, c_vp, c_vp],
@@ -193,6 +194,7 @@ _SPECIAL = {
     "fs_sgd_tensor_chunks": ([c_ll, c_int, c_int, c_int], c_ll),
     "fs_refresh_chunk_elems": ([], c_int),
     "fs_refresh_entry_chunks": ([ctypes.POINTER(RefreshEntry)], c_ll),
+    "fs_refresh_entry_chunks_infer": ([ctypes.POINTER(RefreshEntry)], c_ll),
     "fs_loss_up_workspace_bytes": ([ctypes.POINTER(LogitsDesc)], c_ll),
     "fs_ohem_select_workspace_bytes": ([c_ll], c_ll),
     "fs_train_batch_args_bytes": ([c_int], c_ll),

@@ -89,7 +89,7 @@ def conv_flops(d):
 
 
 def conv_bytes(d):
-    es = 2 if d.dtype == _lib.FS_BF16 else 4
+    es = K.elem_size(d.dtype)
     in_px = d.N * (d.vr_H * d.vr_W if d.vr_H > 0 else d.H * d.W)
     return es * (in_px * d.Cin + d.Cout * d.R * d.S * d.Cin + d.N * d.Ho * d.Wo * d.Cout)
 
@@ -121,7 +121,7 @@ def _graph_time_ms(fn, reps=20, rounds=3):
 
 def time_entry(family, d, device="cuda"):
     """Device time (ms) of one launch of this geometry on random operands."""
-    dt = torch.bfloat16 if d.dtype == _lib.FS_BF16 else torch.float32
+    dt = {_lib.FS_F32: torch.float32, _lib.FS_BF16: torch.bfloat16, _lib.FS_F16: torch.float16}[d.dtype]
     fam = family & 0xff
     in_h, in_w = (d.vr_H, d.vr_W) if d.vr_H > 0 else (d.H, d.W)
     x = torch.randn(d.N * in_h * in_w * d.x_cs, device=device).to(dt)

@@ -10,9 +10,13 @@
 namespace fs {
 
 typedef uint16_t bf16_t;   // raw bfloat16 storage
+struct f16_t { uint16_t bits; };   // raw IEEE half storage (FS_F16): a type of its own, bf16_t being a plain uint16_t; never computed in
+                                   // directly - Elem<f16_t> converts at the loads and stores
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 // ---- error reporting (thread-local, never aborts) ---------------------------------------------
@@ -142,8 +146,27 @@ __device__ __forceinline__ bool arrive_last(unsigned int* counter, unsigned int 
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline int elem_size(int dtype) { return dtype == FS_BF16 ? 2 : 4; }
+inline int elem_size(int dtype) { return dtype == FS_F32 ? 4 : 2; }
 inline int vec_elems(int dtype) { return 16 / elem_size(dtype); }
+// dtype validation, in two grades: the inference-side entry points take the three storage types, everything that trains (BatchNorm
+// passes, gradients, loss heads, optimizer packs, convolutions with statistics or training flags) stays fp32 / bf16
+inline bool dtype_ok(int dtype) { return dtype == FS_F32 || dtype == FS_BF16 || dtype == FS_F16; }
+inline bool dtype_train_ok(int dtype) { return dtype == FS_F32 || dtype == FS_BF16; }
+// The dtype switch of an inference-side entry point, written once: runs the statement(s) with T = float / bf16_t / f16_t.  The caller has
+// checked dtype_ok(dtype).  (The training-side entry points keep their two-way `dtype == FS_F32 ? float : bf16_t` - they refuse FS_F16
+// before they get there, and so instantiate nothing for it.)
+#define FS_DTYPE_SWITCH(dtype, T, ...)                                  \
+    do {                                                                \
+        if ((dtype) == FS_F32) { typedef float T; __VA_ARGS__; }        \
+        else if ((dtype) == FS_F16) { typedef fs::f16_t T; __VA_ARGS__; } \
+        else { typedef fs::bf16_t T; __VA_ARGS__; }                     \
+    } while (0)
+// ... and its two-way form for the kernels that exist for the 16-bit storage types only (elem_size(dtype) == 2 checked by the caller)
+#define FS_DTYPE16_SWITCH(dtype, T, ...)                                \
+    do {                                                                \
+        if ((dtype) == FS_F16) { typedef fs::f16_t T; __VA_ARGS__; }    \
+        else { typedef fs::bf16_t T; __VA_ARGS__; }                     \
+    } while (0)
 
 // ---- bf16 <-> f32 ------------------------------------------------------------------------------
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
@@ -156,6 +179,31 @@ __device__ __forceinline__ uint32_t pack2_bf16(float lo, float hi) {
     v[0] = (__bf16)lo;
     v[1] = (__bf16)hi;
     return __builtin_bit_cast(uint32_t, v);
+}
+
+
+// ---- f16 <-> f32 -------------------------------------------------------------------------------
+// fp32 -> fp16 (include/fasterseg_hip.h states the rule): round to nearest even; a finite value beyond +-65504 - one that would round up
+// to infinity included - and an infinity are stored as +-65504; NaN stays NaN.  The clamp runs BEFORE the conversion (v_med3_f32), so
+// 65519.99 -> 65504 and never 65520 -> inf; v_med3 answers min3 when an operand is NaN, hence the select around it.
+constexpr float F16_MAX = 65504.f;
+__device__ __forceinline__ float f16_clamp(float v) {
+    const float c = __builtin_amdgcn_fmed3f(v, -F16_MAX, F16_MAX);
+    return v != v ? v : c;
+}
+__device__ __forceinline__ float f16_to_f32(f16_t v) { return (float)__builtin_bit_cast(_Float16, v.bits); }
+__device__ __forceinline__ f16_t f32_to_f16(float f) { return f16_t{__builtin_bit_cast(uint16_t, (_Float16)f16_clamp(f))}; }
+__device__ __forceinline__ uint32_t pack2_f16(float lo, float hi) {          // one v_cvt_pk_f16_f32 per pair
+    f16x2_t v;
+    v[0] = (_Float16)f16_clamp(lo);
+    v[1] = (_Float16)f16_clamp(hi);
+    return __builtin_bit_cast(uint32_t, v);
+}
+// four consecutive fp16 channels (one 8-byte load): the logits readers' quad (resize.hip, eval.hip, eval_ms.hip)
+__device__ __forceinline__ void f16_load4(const f16_t* p, float* o) {
+    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
+    const f16x4 v = __builtin_bit_cast(f16x4, *reinterpret_cast<const uint2*>(p));
+    o[0] = (float)v[0]; o[1] = (float)v[1]; o[2] = (float)v[2]; o[3] = (float)v[3];
 }
 
 template <typename T> struct Elem;
@@ -190,6 +238,22 @@ template <> struct Elem<bf16_t> {
         u32x4 v;
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = pack2_bf16(in[2 * i], in[2 * i + 1]);
+        return v;
+    }
+};
+template <> struct Elem<f16_t> {
+    static constexpr int VEC = 8;
+    __device__ static __forceinline__ float load(const f16_t* p) { return f16_to_f32(*p); }
+    __device__ static __forceinline__ void store(f16_t* p, float v) { *p = f32_to_f16(v); }
+    __device__ static __forceinline__ void unpack(const u32x4& v, float* out) {
+        const f16x8 h = __builtin_bit_cast(f16x8, v);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) out[i] = (float)h[i];
+    }
+    __device__ static __forceinline__ u32x4 pack(const float* in) {
+        u32x4 v;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = pack2_f16(in[2 * i], in[2 * i + 1]);
         return v;
     }
 };
@@ -251,6 +315,11 @@ template <> struct Mma<bf16_t> {
     static __device__ __forceinline__ void run(const u32x4& a, const u32x4& b, f32x16& c) {
         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
                                                     0, 0, 0);
+    }
+};
+template <> struct Mma<f16_t> {
+    static __device__ __forceinline__ void run(const u32x4& a, const u32x4& b, f32x16& c) {
+        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     }
 };
 

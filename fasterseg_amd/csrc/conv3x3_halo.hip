@@ -511,6 +511,11 @@ template <> struct Mma16<bf16_t> {
         c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
     }
 };
+template <> struct Mma16<f16_t> {
+    static __device__ __forceinline__ void run(const u32x4& a, const u32x4& b, f32x4& c) {
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    }
+};
 
 template <typename T, bool VRES>
 __global__ __launch_bounds__(256) void conv3x3_halo_ksplit16_kernel(HaloArgs p) {
@@ -797,23 +802,19 @@ extern "C" long long fs_packed_weight_frag_elems(int Cout, int Cin, int dtype) {
 extern "C" fs_status fs_pack_weight_frag(void* stream, const float* w, long long o_stride, long long i_stride, int Cout, int Cin,
                                          int dtype, void* out) {
     FS_REQUIRE(w && out && Cout > 0 && Cin > 0, FS_ERR_INVALID, "fs_pack_weight_frag: bad argument");
-    FS_REQUIRE(dtype == FS_F32 || dtype == FS_BF16, FS_ERR_INVALID, "fs_pack_weight_frag: bad dtype");
+    FS_REQUIRE(dtype_ok(dtype), FS_ERR_INVALID, "fs_pack_weight_frag: bad dtype");
     const int vec = vec_elems(dtype), ck = 4 * vec;
     const int nchunks = (Cin + ck - 1) / ck;
     const long long total = fs_packed_weight_frag_elems(Cout, Cin, dtype);
     long long g = (total + 255) / 256;
     if (g > 8192) g = 8192;
-    if (dtype == FS_F32)
-        FS_LAUNCH((pack_weight_frag_kernel<float>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, w, o_stride, i_stride,
-                           Cout, Cin, nchunks, total, (float*)out);
-    else
-        FS_LAUNCH((pack_weight_frag_kernel<bf16_t>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, w, o_stride, i_stride,
-                           Cout, Cin, nchunks, total, (bf16_t*)out);
+    FS_DTYPE_SWITCH(dtype, T, FS_LAUNCH((pack_weight_frag_kernel<T>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, w, o_stride,
+                                        i_stride, Cout, Cin, nchunks, total, (T*)out));
     return check_launch("fs_pack_weight_frag");
 }
 
 extern "C" fs_status fs_conv3x3_halo_plan(const fs_conv_desc* d, int has_stats, int* tile, int* ksplit, long long* workgroups) {
-    FS_REQUIRE(d && (d->dtype == FS_F32 || d->dtype == FS_BF16) && d->N > 0 && d->Ho > 0 && d->Wo > 0 && d->Cin > 0 && d->Cout > 0 &&
+    FS_REQUIRE(d && dtype_ok(d->dtype) && d->N > 0 && d->Ho > 0 && d->Wo > 0 && d->Cin > 0 && d->Cout > 0 &&
                    (d->stride == 1 || d->stride == 2),
                FS_ERR_INVALID, "fs_conv3x3_halo_plan: bad descriptor");
     FS_REQUIRE((d->flags & (FS_CONV_KSPLIT | FS_CONV_NO_KSPLIT)) != (FS_CONV_KSPLIT | FS_CONV_NO_KSPLIT), FS_ERR_INVALID,
@@ -831,7 +832,8 @@ extern "C" fs_status fs_conv3x3_halo_plan(const fs_conv_desc* d, int has_stats, 
 extern "C" fs_status fs_conv3x3_s1_fwd(void* stream, const fs_conv_desc* d, const void* x, const void* w_frag, const float* scale,
                                        const float* shift, void* y, float* stats) {
     FS_REQUIRE(d && x && w_frag && y, FS_ERR_INVALID, "fs_conv3x3_s1_fwd: null argument");
-    FS_REQUIRE(d->dtype == FS_F32 || d->dtype == FS_BF16, FS_ERR_INVALID, "fs_conv3x3_s1_fwd: bad dtype");
+    FS_REQUIRE(dtype_ok(d->dtype), FS_ERR_INVALID, "fs_conv3x3_s1_fwd: bad dtype");
+    FS_REQUIRE(d->dtype != FS_F16 || !stats, FS_ERR_UNSUPPORTED, "fs_conv3x3_s1_fwd: FS_F16 is inference only (no BN statistics)");
     FS_REQUIRE(d->R == 3 && d->S == 3 && (d->stride == 1 || d->stride == 2) && d->pad == 1 && d->Ho == (d->H - 1) / d->stride + 1 &&
                    d->Wo == (d->W - 1) / d->stride + 1 && !(d->flags & ~(FS_CONV_RELU | FS_CONV_TILE_MASK | FS_CONV_KSPLIT16 | FS_CONV_NO_KSPLIT)),
                FS_ERR_UNSUPPORTED, "fs_conv3x3_s1_fwd: only 3x3 / stride 1 or 2 / pad 1 (got %dx%d s%d p%d)", d->R, d->S, d->stride, d->pad);
@@ -864,7 +866,6 @@ extern "C" fs_status fs_conv3x3_s1_fwd(void* stream, const fs_conv_desc* d, cons
     FS_REQUIRE(pl.ksplit >= 0, FS_ERR_UNSUPPORTED, "fs_conv3x3_s1_fwd: the K-split form is stride 1 without BN statistics only");
     if (!(aligned16(y) && (d->y_cs % vec == 0))) a.flags |= CONV_SCALAR_STORE;
     FS_CENSUS(FS_CENSUS_CONV_HALO | (stats ? FS_CENSUS_STATS : 0), d);
-    if (d->dtype == FS_F32) dispatch_halo<float>((hipStream_t)stream, a, pl, d->stride);
-    else dispatch_halo<bf16_t>((hipStream_t)stream, a, pl, d->stride);
+    FS_DTYPE_SWITCH(d->dtype, T, dispatch_halo<T>((hipStream_t)stream, a, pl, d->stride));
     return check_launch("fs_conv3x3_s1_fwd");
 }

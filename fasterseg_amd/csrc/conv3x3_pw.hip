@@ -1,5 +1,5 @@
 // 3x3 / stride 1 / pad 1 LDS-halo convolution with the pointwise (1x1) convolution behind it in the same launch, inference epilogues,
-// NHWC, bf16 (gfx950).
+// NHWC, 16-bit storage types (bf16, fp16; gfx950).
 //
 // The tail of every derived network ends in heads.conv_3x3 -> heads.conv_1x1 (model_seg.py:345, seg_oprs.py Head), and an arm of
 // `_arm_up_refine` (model_seg.py:322-334) is a 3x3 whose only eval-mode reader is a 1x1.  As separate launches the 3x3's map is written
@@ -304,12 +304,12 @@ static int plan_pw_rows(const fs_conv_pw_desc* d) {
 
 static fs_status check_pw(const fs_conv_pw_desc* d, const char* who) {
     FS_REQUIRE(d, FS_ERR_INVALID, "%s: null descriptor", who);
-    FS_REQUIRE(d->dtype == FS_F32 || d->dtype == FS_BF16, FS_ERR_INVALID, "%s: bad dtype %d", who, d->dtype);
+    FS_REQUIRE(dtype_ok(d->dtype), FS_ERR_INVALID, "%s: bad dtype %d", who, d->dtype);
     FS_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->C3 > 0 && d->Cout > 0, FS_ERR_INVALID,
                "%s: bad geometry N%d %dx%d channels %d -> %d -> %d", who, d->N, d->H, d->W, d->Cin, d->C3, d->Cout);
     FS_REQUIRE(!(d->flags & ~(FS_PW_RELU_3X3 | FS_PW_RELU_POST | FS_PW_ROWS_MASK)), FS_ERR_INVALID, "%s: unknown flags 0x%x", who, d->flags);
     FS_REQUIRE((d->flags & FS_PW_ROWS_MASK) != FS_PW_ROWS_MASK, FS_ERR_INVALID, "%s: FS_PW_ROWS4 and FS_PW_ROWS8 exclude each other", who);
-    FS_REQUIRE(d->dtype == FS_BF16, FS_ERR_UNSUPPORTED, "%s: bf16 only (fp32 keeps the separate launches)", who);
+    FS_REQUIRE(elem_size(d->dtype) == 2, FS_ERR_UNSUPPORTED, "%s: 16-bit storage types only (FS_BF16 / FS_F16; before FS_F16: bf16 only) - fp32 keeps the separate launches", who);
     const int vec = vec_elems(d->dtype);
     FS_REQUIRE(d->Cin % vec == 0 && d->x_cs % vec == 0 && d->x_cs >= d->Cin && d->y_cs >= d->Cout, FS_ERR_INVALID,
                "%s: bad channel counts/strides (Cin %d, x_cs %d, y_cs %d)", who, d->Cin, d->x_cs, d->y_cs);
@@ -353,7 +353,7 @@ extern "C" fs_status fs_conv3x3_pw_fwd(void* stream, const fs_conv_pw_desc* d, c
     a.relu3 = (d->flags & FS_PW_RELU_3X3) != 0;
     a.relu2 = (d->flags & FS_PW_RELU_POST) != 0;
     a.scalar_store = !(aligned16(y) && (d->y_cs % vec == 0));
-    if (plan_pw_rows(d) == 8) launch_pw<bf16_t, 2>((hipStream_t)stream, a);
-    else launch_pw<bf16_t, 1>((hipStream_t)stream, a);
+    if (plan_pw_rows(d) == 8) FS_DTYPE16_SWITCH(d->dtype, T, launch_pw<T, 2>((hipStream_t)stream, a));
+    else FS_DTYPE16_SWITCH(d->dtype, T, launch_pw<T, 1>((hipStream_t)stream, a));
     return check_launch("fs_conv3x3_pw_fwd");
 }

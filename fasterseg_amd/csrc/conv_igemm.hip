@@ -522,8 +522,7 @@ template <typename T> static void launch_reduce_t(hipStream_t st, const ConvArgs
               a.shift, (a.flags & FS_CONV_RELU) ? 1 : 0, (T*)a.y, a.y_cs, a.stats, rows);
 }
 void launch_splitk_reduce(hipStream_t st, const ConvArgs& a, int dtype, float* ws, int slices) {
-    if (dtype == FS_F32) launch_reduce_t<float>(st, a, ws, slices);
-    else launch_reduce_t<bf16_t>(st, a, ws, slices);
+    FS_DTYPE_SWITCH(dtype, T, launch_reduce_t<T>(st, a, ws, slices));
 }
 
 constexpr long long SPLITK_TARGET_BLOCKS = 1024;
@@ -659,7 +658,10 @@ extern "C" fs_status fs_conv2d_fwd(void* stream, const fs_conv_desc* d, const vo
 fs_status fs::conv_prepare(const fs_conv_desc* d, const void* x, const void* w_packed, const float* scale, const float* shift, void* y,
                            float* stats, ConvArgs* out) {
     FS_REQUIRE(d && x && w_packed && y, FS_ERR_INVALID, "fs_conv2d_fwd: null argument");
-    FS_REQUIRE(d->dtype == FS_F32 || d->dtype == FS_BF16, FS_ERR_INVALID, "fs_conv2d_fwd: bad dtype %d", d->dtype);
+    FS_REQUIRE(dtype_ok(d->dtype), FS_ERR_INVALID, "fs_conv2d_fwd: bad dtype %d", d->dtype);
+    // FS_F16 is an inference storage type: no BatchNorm statistics, no data-gradient gather, no accumulation (nothing is instantiated apart)
+    FS_REQUIRE(d->dtype != FS_F16 || (!stats && !(d->flags & (FS_CONV_TRANSPOSED | FS_CONV_ACCUM | FS_CONV_RELU_TAIL)) && d->bn_groups <= 1),
+               FS_ERR_UNSUPPORTED, "fs_conv2d_fwd: FS_F16 is inference only (no stats, no FS_CONV_TRANSPOSED / FS_CONV_ACCUM / FS_CONV_RELU_TAIL)");
     const int vec = vec_elems(d->dtype);
     FS_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->Ho > 0 && d->Wo > 0, FS_ERR_INVALID,
                "fs_conv2d_fwd: non-positive dimension");
@@ -757,8 +759,7 @@ extern "C" fs_status fs_conv2d_fwd_ws(void* stream, const fs_conv_desc* d, const
         }
     }
     const int old_force = (g_force_cfg >= 100 || g_force_cfg < 0) ? -1 : g_force_cfg;       // igemm2 codes mean nothing to these kernels
-    if (d->dtype == FS_F32) dispatch<float>((hipStream_t)stream, a, old_force, (float*)workspace, ws_bytes);
-    else dispatch<bf16_t>((hipStream_t)stream, a, old_force, (float*)workspace, ws_bytes);
+    FS_DTYPE_SWITCH(d->dtype, T, dispatch<T>((hipStream_t)stream, a, old_force, (float*)workspace, ws_bytes));
     return check_launch("fs_conv2d_fwd");
 }
 
@@ -784,8 +785,7 @@ fs_status fs::conv_launch_group(void* stream, const fs_conv_desc* const* descs, 
         FS_CENSUS(FS_CENSUS_CONV_IGEMM | (a.stats ? FS_CENSUS_STATS : 0), descs[i]);
         if (igemm2_launch((hipStream_t)stream, a, descs[i]->dtype, g_force_cfg, nullptr, 0, false, nullptr)) continue;
         const int old_force = (g_force_cfg >= 100 || g_force_cfg < 0) ? -1 : g_force_cfg;
-        if (descs[i]->dtype == FS_F32) dispatch<float>((hipStream_t)stream, a, old_force, nullptr, 0);
-        else dispatch<bf16_t>((hipStream_t)stream, a, old_force, nullptr, 0);
+        FS_DTYPE_SWITCH(descs[i]->dtype, T, dispatch<T>((hipStream_t)stream, a, old_force, nullptr, 0));
     }
     return check_launch("fs_conv2d_fwd");
 }

@@ -692,8 +692,7 @@ bool igemm2_group_launch(hipStream_t st, ConvArgs* a, int n, int dtype) {
         grid += igemm2_configure(grp.p[i], es, CFG2[cfg].bm, CFG2[cfg].bn, 1, nullptr);
     }
     for (int i = n; i <= FS_MAX_GROUP; ++i) grp.blk_start[i] = grid;
-    if (dtype == FS_F32) launch2_group<float>(st, grp, cfg, grid);
-    else launch2_group<bf16_t>(st, grp, cfg, grid);
+    FS_DTYPE_SWITCH(dtype, T, launch2_group<T>(st, grp, cfg, grid));
     return true;
 }
 
@@ -771,8 +770,7 @@ bool igemm2_launch(hipStream_t st, ConvArgs& a, int dtype, int force_cfg, float*
     ConvArgs k = a;                                  // the launch fields go into a copy: `a` stays usable for conv_igemm.hip's kernels
     const int grid = igemm2_configure(k, es, bm, bn, slices, ws);
     slices = k.slices;
-    if (dtype == FS_F32) launch2<float>(st, k, cfg, grid);
-    else launch2<bf16_t>(st, k, cfg, grid);
+    FS_DTYPE_SWITCH(dtype, T, launch2<T>(st, k, cfg, grid));
     a.slices = slices;                               // (launch_splitk_reduce reads M / Cout / y / scale ... of `a`)
     if (slices > 1) {
         if (defer_reduce) {

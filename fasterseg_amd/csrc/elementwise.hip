@@ -488,9 +488,19 @@ static fs_status check_slice(const char* fn, const void* p, int cs, int C, int d
 
 using namespace fs;
 
-#define DT_DISPATCH(dtype, ...)                         \
+// the training-side kernels: fp32 / bf16, anything else (FS_F16 included) is refused before the launch
+#define DT_DISPATCH(dtype, ...)                                  \
+    if ((dtype) == FS_F32) { typedef float T; __VA_ARGS__ }      \
+    else if ((dtype) == FS_BF16) { typedef bf16_t T; __VA_ARGS__ } \
+    else { FS_REQUIRE(false, FS_ERR_INVALID, "bad dtype %d (fp32 / bf16 only)", (int)(dtype)); }
+// ... and the same switch behind group_driver, which has validated the dtype (void launch callbacks)
+#define DT_DISPATCH2(dtype, ...)                            \
     if ((dtype) == FS_F32) { typedef float T; __VA_ARGS__ } \
     else { typedef bf16_t T; __VA_ARGS__ }
+// the inference-side ones (weight packs, layout conversions, channel copies, folded BatchNorm): the three storage types
+#define DT_DISPATCH_INFER(fn, dtype, ...)                                      \
+    FS_REQUIRE(dtype_ok(dtype), FS_ERR_INVALID, fn ": bad dtype %d", (int)(dtype)); \
+    FS_DTYPE_SWITCH(dtype, T, __VA_ARGS__);
 
 extern "C" long long fs_packed_weight_elems(int Cout, int R, int S, int Cin) { return (long long)Cout * R * S * Cin; }
 
@@ -498,9 +508,8 @@ extern "C" fs_status fs_pack_weight(void* stream, const float* w, long long o_st
                                     int R, int S, int dtype, int tflip, void* out) {
     FS_REQUIRE(w && out, FS_ERR_INVALID, "fs_pack_weight: null pointer");
     FS_REQUIRE(Cout > 0 && Cin > 0 && R > 0 && S > 0, FS_ERR_INVALID, "fs_pack_weight: bad shape");
-    FS_REQUIRE(dtype == FS_F32 || dtype == FS_BF16, FS_ERR_INVALID, "fs_pack_weight: bad dtype");
     const long long total = (long long)Cout * Cin * R * S;
-    DT_DISPATCH(dtype, FS_LAUNCH((pack_weight_kernel<T>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, w,
+    DT_DISPATCH_INFER("fs_pack_weight", dtype, FS_LAUNCH((pack_weight_kernel<T>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, w,
                                           o_stride, i_stride, Cout, Cin, R, S, tflip, (T*)out);)
     return check_launch("fs_pack_weight");
 }
@@ -519,7 +528,7 @@ extern "C" fs_status fs_nchw_to_nhwc(void* stream, int N, int C, int H, int W, c
     FS_REQUIRE(x && y && N > 0 && C > 0 && H > 0 && W > 0, FS_ERR_INVALID, "fs_nchw_to_nhwc: bad argument");
     FS_REQUIRE(c_pad >= C && y_cs >= c_pad, FS_ERR_INVALID, "fs_nchw_to_nhwc: need C <= c_pad <= y_cs");
     dim3 grid((H * W + 63) / 64, N);
-    DT_DISPATCH(dtype, FS_LAUNCH((nchw_to_nhwc_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, C, H * W, x, (T*)y,
+    DT_DISPATCH_INFER("fs_nchw_to_nhwc", dtype, FS_LAUNCH((nchw_to_nhwc_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, C, H * W, x, (T*)y,
                                           y_cs, c_pad);)
     return check_launch("fs_nchw_to_nhwc");
 }
@@ -527,7 +536,7 @@ extern "C" fs_status fs_nchw_to_nhwc(void* stream, int N, int C, int H, int W, c
 extern "C" fs_status fs_nhwc_to_nchw(void* stream, int N, int C, int H, int W, const void* x, int x_cs, int dtype, float* y) {
     FS_REQUIRE(x && y && N > 0 && C > 0 && H > 0 && W > 0 && x_cs >= C, FS_ERR_INVALID, "fs_nhwc_to_nchw: bad argument");
     dim3 grid((H * W + 63) / 64, N);
-    DT_DISPATCH(dtype, FS_LAUNCH((nhwc_to_nchw_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, C, H * W,
+    DT_DISPATCH_INFER("fs_nhwc_to_nchw", dtype, FS_LAUNCH((nhwc_to_nchw_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, C, H * W,
                                           (const T*)x, x_cs, y);)
     return check_launch("fs_nhwc_to_nchw");
 }
@@ -535,25 +544,27 @@ extern "C" fs_status fs_nhwc_to_nchw(void* stream, int N, int C, int H, int W, c
 extern "C" fs_status fs_copy_channels(void* stream, long long pixels, int C, const void* x, int x_cs, void* y, int y_cs,
                                       int dtype) {
     fs_status s;
+    FS_REQUIRE(dtype_ok(dtype), FS_ERR_INVALID, "fs_copy_channels: bad dtype %d", dtype);
     if ((s = check_slice("fs_copy_channels", x, x_cs, C, dtype)) != FS_OK) return s;
     if ((s = check_slice("fs_copy_channels", y, y_cs, C, dtype)) != FS_OK) return s;
     const int cv = C / vec_elems(dtype);
     const EwArgs a{pixels, cv, x, x_cs, y, y_cs, nullptr, nullptr, 0};
     FS_NOTE_BYTES((double)pixels * C * elem_size(dtype) * 2);
-    DT_DISPATCH(dtype, FS_LAUNCH((ew_kernel<T, EW_COPY>), dim3(grid_for(pixels * cv)), dim3(256), 0, (hipStream_t)stream, a);)
+    DT_DISPATCH_INFER("fs_copy_channels", dtype, FS_LAUNCH((ew_kernel<T, EW_COPY>), dim3(grid_for(pixels * cv)), dim3(256), 0, (hipStream_t)stream, a);)
     return check_launch("fs_copy_channels");
 }
 
 extern "C" fs_status fs_affine_act(void* stream, long long pixels, int C, const void* x, int x_cs, const float* scale,
                                    const float* shift, void* y, int y_cs, int dtype, int relu) {
     fs_status s;
+    FS_REQUIRE(dtype_ok(dtype), FS_ERR_INVALID, "fs_affine_act: bad dtype %d", dtype);
     if ((s = check_slice("fs_affine_act", x, x_cs, C, dtype)) != FS_OK) return s;
     if ((s = check_slice("fs_affine_act", y, y_cs, C, dtype)) != FS_OK) return s;
     FS_REQUIRE(scale && shift, FS_ERR_INVALID, "fs_affine_act: null scale/shift");
     const int cv = C / vec_elems(dtype);
     const EwArgs a{pixels, cv, x, x_cs, y, y_cs, scale, shift, relu};
     FS_NOTE_BYTES((double)pixels * C * elem_size(dtype) * 2);
-    DT_DISPATCH(dtype, FS_LAUNCH((ew_kernel<T, EW_AFFINE>), dim3(grid_for(pixels * cv)), dim3(256), 0, (hipStream_t)stream, a);)
+    DT_DISPATCH_INFER("fs_affine_act", dtype, FS_LAUNCH((ew_kernel<T, EW_AFFINE>), dim3(grid_for(pixels * cv)), dim3(256), 0, (hipStream_t)stream, a);)
     return check_launch("fs_affine_act");
 }
 
@@ -915,8 +926,8 @@ fs_status fs::bn_stats_group(void* stream, const BnFwdCall* c, const int* idx, i
     hipStream_t st = (hipStream_t)stream;
     return group_driver<BnFwdCall, ChanReduceArgs>(c, idx, n, "fs_channel_stats", 1, 0, prep_stats, [&](int dtype, const Packed<ChanReduceArgs>& pk, int m) {
         const ChanReduceArgs& a = pk.g.p[0];
-        if (m == 1) { DT_DISPATCH(dtype, FS_LAUNCH((chan_reduce_kernel<T, 0>), dim3(a.nbx, pk.grid / a.nbx), dim3(256), 0, st, a);) }
-        else { DT_DISPATCH(dtype, FS_LAUNCH((chan_reduce_group_kernel<T, 0>), dim3(pk.grid), dim3(256), 0, st, pk.g);) }
+        if (m == 1) { DT_DISPATCH2(dtype, FS_LAUNCH((chan_reduce_kernel<T, 0>), dim3(a.nbx, pk.grid / a.nbx), dim3(256), 0, st, a);) }
+        else { DT_DISPATCH2(dtype, FS_LAUNCH((chan_reduce_group_kernel<T, 0>), dim3(pk.grid), dim3(256), 0, st, pk.g);) }
     });
 }
 
@@ -924,8 +935,8 @@ fs_status fs::bn_apply_group(void* stream, const BnFwdCall* c, const int* idx, i
     hipStream_t st = (hipStream_t)stream;
     return group_driver<BnFwdCall, BnApplyArgs>(c, idx, n, "fs_bn_train_apply", 2, 0, prep_apply, [&](int dtype, const Packed<BnApplyArgs>& pk, int m) {
         const BnApplyArgs& a = pk.g.p[0];
-        if (m == 1) { DT_DISPATCH(dtype, FS_LAUNCH((bn_train_apply_kernel<T>), dim3(pk.grid), dim3(256), 0, st, a);) }
-        else { DT_DISPATCH(dtype, FS_LAUNCH((bn_train_apply_group_kernel<T>), dim3(pk.grid), dim3(256), 0, st, pk.g);) }
+        if (m == 1) { DT_DISPATCH2(dtype, FS_LAUNCH((bn_train_apply_kernel<T>), dim3(pk.grid), dim3(256), 0, st, a);) }
+        else { DT_DISPATCH2(dtype, FS_LAUNCH((bn_train_apply_group_kernel<T>), dim3(pk.grid), dim3(256), 0, st, pk.g);) }
     });
 }
 
@@ -933,8 +944,8 @@ fs_status fs::bn_bwd_reduce_group(void* stream, const BnBwdCall* c, const int* i
     hipStream_t st = (hipStream_t)stream;
     return group_driver<BnBwdCall, ChanReduceArgs>(c, idx, n, "fs_bn_bwd_reduce", 2, 1, prep_bwd_reduce, [&](int dtype, const Packed<ChanReduceArgs>& pk, int m) {
         const ChanReduceArgs& a = pk.g.p[0];
-        if (m == 1) { DT_DISPATCH(dtype, FS_LAUNCH((chan_reduce_kernel<T, 1>), dim3(a.nbx, pk.grid / a.nbx), dim3(256), 0, st, a);) }
-        else { DT_DISPATCH(dtype, FS_LAUNCH((chan_reduce_group_kernel<T, 1>), dim3(pk.grid), dim3(256), 0, st, pk.g);) }
+        if (m == 1) { DT_DISPATCH2(dtype, FS_LAUNCH((chan_reduce_kernel<T, 1>), dim3(a.nbx, pk.grid / a.nbx), dim3(256), 0, st, a);) }
+        else { DT_DISPATCH2(dtype, FS_LAUNCH((chan_reduce_group_kernel<T, 1>), dim3(pk.grid), dim3(256), 0, st, pk.g);) }
     });
 }
 
@@ -942,8 +953,8 @@ fs_status fs::bn_bwd_apply_group(void* stream, const BnBwdCall* c, const int* id
     hipStream_t st = (hipStream_t)stream;
     return group_driver<BnBwdCall, BnBwdApplyArgs>(c, idx, n, "fs_bn_bwd_apply", 3, 1, prep_bwd_apply, [&](int dtype, const Packed<BnBwdApplyArgs>& pk, int m) {
         const BnBwdApplyArgs& a = pk.g.p[0];
-        if (m == 1) { DT_DISPATCH(dtype, FS_LAUNCH((bn_bwd_apply_kernel<T>), dim3(pk.grid), dim3(256), 0, st, a);) }
-        else { DT_DISPATCH(dtype, FS_LAUNCH((bn_bwd_apply_group_kernel<T>), dim3(pk.grid), dim3(256), 0, st, pk.g);) }
+        if (m == 1) { DT_DISPATCH2(dtype, FS_LAUNCH((bn_bwd_apply_kernel<T>), dim3(pk.grid), dim3(256), 0, st, a);) }
+        else { DT_DISPATCH2(dtype, FS_LAUNCH((bn_bwd_apply_group_kernel<T>), dim3(pk.grid), dim3(256), 0, st, pk.g);) }
     });
 }
 

@@ -29,6 +29,9 @@ template <> struct Quad4<bf16_t> {
         o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
     }
 };
+template <> struct Quad4<f16_t> {
+    static __device__ __forceinline__ void load(const f16_t* p, float* o) { f16_load4(p, o); }
+};
 
 // one lane: 4 consecutive output columns of one output row, all classes (4 at a time)
 template <typename T>
@@ -162,7 +165,7 @@ extern "C" fs_status fs_bilinear_argmax(void* stream, const fs_resize_desc* d, c
     FS_REQUIRE(d && x && classes, FS_ERR_INVALID, "fs_bilinear_argmax: null argument");
     FS_REQUIRE(d->N > 0 && d->Hi > 0 && d->Wi > 0 && d->Ho > 0 && d->Wo > 0 && d->C > 0 && d->C <= 256, FS_ERR_INVALID,
                "fs_bilinear_argmax: bad dimension (C must be in 1..256 for a uint8 class map)");
-    FS_REQUIRE(d->dtype == FS_F32 || d->dtype == FS_BF16, FS_ERR_INVALID, "fs_bilinear_argmax: bad dtype");
+    FS_REQUIRE(dtype_ok(d->dtype), FS_ERR_INVALID, "fs_bilinear_argmax: bad dtype");
     FS_REQUIRE(d->x_cs >= ((d->C + 3) / 4) * 4 && d->x_cs % 4 == 0, FS_ERR_INVALID,
                "fs_bilinear_argmax: the logits' channel stride must be padded to a multiple of 4 (got %d for C=%d)", d->x_cs, d->C);
     FS_REQUIRE(d->Wo % 4 == 0, FS_ERR_UNSUPPORTED, "fs_bilinear_argmax: output width %d must be a multiple of 4", d->Wo);
@@ -176,23 +179,15 @@ extern "C" fs_status fs_bilinear_argmax(void* stream, const fs_resize_desc* d, c
         const long long total8 = (long long)d->N * d->Ho * (d->Wo / 8);
         long long g8 = (total8 + 255) / 256;
         if (g8 > 16384) g8 = 16384;
-        if (d->dtype == FS_F32)
-            FS_LAUNCH((bilinear_argmax8_kernel<float, 5>), dim3((unsigned)g8), dim3(256), 0, st, d->N, d->Hi, d->Wi, d->Ho, d->Wo, d->C,
-                               rh, rw, (const float*)x, d->x_cs, classes);
-        else
-            FS_LAUNCH((bilinear_argmax8_kernel<bf16_t, 5>), dim3((unsigned)g8), dim3(256), 0, st, d->N, d->Hi, d->Wi, d->Ho, d->Wo, d->C,
-                               rh, rw, (const bf16_t*)x, d->x_cs, classes);
+        FS_DTYPE_SWITCH(d->dtype, T, FS_LAUNCH((bilinear_argmax8_kernel<T, 5>), dim3((unsigned)g8), dim3(256), 0, st, d->N, d->Hi, d->Wi, d->Ho,
+                                               d->Wo, d->C, rh, rw, (const T*)x, d->x_cs, classes));
         return check_launch("fs_bilinear_argmax");
     }
     const long long total = (long long)d->N * d->Ho * (d->Wo / 4);
     long long g = (total + 255) / 256;
     if (g > 16384) g = 16384;
-    if (d->dtype == FS_F32)
-        FS_LAUNCH((bilinear_argmax_kernel<float>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, d->N, d->Hi, d->Wi, d->Ho,
-                           d->Wo, d->C, rh, rw, (const float*)x, d->x_cs, classes);
-    else
-        FS_LAUNCH((bilinear_argmax_kernel<bf16_t>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, d->N, d->Hi, d->Wi,
-                           d->Ho, d->Wo, d->C, rh, rw, (const bf16_t*)x, d->x_cs, classes);
+    FS_DTYPE_SWITCH(d->dtype, T, FS_LAUNCH((bilinear_argmax_kernel<T>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, d->N, d->Hi, d->Wi,
+                                           d->Ho, d->Wo, d->C, rh, rw, (const T*)x, d->x_cs, classes));
     return check_launch("fs_bilinear_argmax");
 }
 

@@ -32,6 +32,15 @@ template <> struct LoadQuad<bf16_t> {
         return o;
     }
 };
+template <> struct LoadQuad<f16_t> {
+    static __device__ __forceinline__ f32x4 load(const f16_t* p) {
+        f32x4 o;
+        float t[4];
+        f16_load4(p, t);
+        o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = t[3];
+        return o;
+    }
+};
 
 __device__ __forceinline__ long long grid_stride() { return (long long)gridDim.x * blockDim.x; }
 
@@ -276,12 +285,12 @@ extern "C" fs_status fs_eval_score_accumulate(void* stream, const fs_logits_desc
     FS_REQUIRE(d->N >= 1 + flip && d->h > 0 && d->w > 0 && d->H > 0 && d->W > 0 && d->C > 0, FS_ERR_INVALID,
                "fs_eval_score_accumulate: bad logits descriptor (N=%d, %dx%d -> %dx%d, C=%d, flip=%d)", d->N, d->h, d->w, d->H, d->W,
                d->C, flip);
-    FS_REQUIRE(d->dtype == FS_F32 || d->dtype == FS_BF16, FS_ERR_INVALID, "fs_eval_score_accumulate: bad dtype");
+    FS_REQUIRE(dtype_ok(d->dtype), FS_ERR_INVALID, "fs_eval_score_accumulate: bad dtype");
     FS_REQUIRE(d->cs % 4 == 0 && d->cs >= ((d->C + 3) / 4) * 4, FS_ERR_INVALID,
                "fs_eval_score_accumulate: the logits' channel stride must be a multiple of 4 covering C (got %d for C=%d)", d->cs, d->C);
     FS_REQUIRE(rows > 0 && cols > 0 && y0 >= 0 && x0 >= 0 && y0 + rows <= d->H && x0 + cols <= d->W, FS_ERR_INVALID,
                "fs_eval_score_accumulate: rectangle (%d, %d) + %dx%d outside the %dx%d window", y0, x0, rows, cols, d->H, d->W);
-    FS_REQUIRE(aligned(logits, d->dtype == FS_F32 ? 16 : 8), FS_ERR_INVALID, "fs_eval_score_accumulate: misaligned logits");
+    FS_REQUIRE(aligned(logits, 4 * elem_size(d->dtype)), FS_ERR_INVALID, "fs_eval_score_accumulate: misaligned logits");
     ScoreArgs a;
     a.h = d->h; a.w = d->w; a.C = d->C; a.cs = d->cs; a.Wo = d->W; a.flip = flip;
     a.rh = d->H > 1 ? (float)(d->h - 1) / (float)(d->H - 1) : 0.f;
@@ -290,14 +299,11 @@ extern "C" fs_status fs_eval_score_accumulate(void* stream, const fs_logits_desc
     a.canvas_w = canvas_w; a.canvas_cs = canvas_cs; a.cy = cy; a.cx = cx; a.store = store ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
     const unsigned g = grid_for((long long)rows * cols);
-    const double logit_bytes = (double)d->h * d->w * d->cs * (d->dtype == FS_F32 ? 4 : 2) * (1 + flip);
+    const double logit_bytes = (double)d->h * d->w * d->cs * elem_size(d->dtype) * (1 + flip);
     if (classes) {
         FS_REQUIRE(d->C <= 256, FS_ERR_UNSUPPORTED, "fs_eval_score_accumulate: C=%d classes do not fit a uint8 class map", d->C);
         FS_NOTE_BYTES(logit_bytes + (double)rows * cols);
-        if (d->dtype == FS_F32)
-            FS_LAUNCH((eval_score_kernel<float, true>), dim3(g), dim3(256), 0, st, a, (const float*)logits, canvas, classes);
-        else
-            FS_LAUNCH((eval_score_kernel<bf16_t, true>), dim3(g), dim3(256), 0, st, a, (const bf16_t*)logits, canvas, classes);
+        FS_DTYPE_SWITCH(d->dtype, T, FS_LAUNCH((eval_score_kernel<T, true>), dim3(g), dim3(256), 0, st, a, (const T*)logits, canvas, classes));
         return check_launch("fs_eval_score_accumulate");
     }
     FS_REQUIRE(canvas, FS_ERR_INVALID, "fs_eval_score_accumulate: neither a canvas nor a class map");
@@ -307,10 +313,7 @@ extern "C" fs_status fs_eval_score_accumulate(void* stream, const fs_logits_desc
                "fs_eval_score_accumulate: rectangle %dx%d at (%d, %d) outside the %dx%d canvas", rows, cols, cy, cx, canvas_h, canvas_w);
     FS_REQUIRE(aligned(canvas, 16), FS_ERR_INVALID, "fs_eval_score_accumulate: misaligned canvas");
     FS_NOTE_BYTES(logit_bytes + (double)rows * cols * ((d->C + 3) / 4) * 16 * (store ? 1 : 2));
-    if (d->dtype == FS_F32)
-        FS_LAUNCH((eval_score_kernel<float, false>), dim3(g), dim3(256), 0, st, a, (const float*)logits, canvas, classes);
-    else
-        FS_LAUNCH((eval_score_kernel<bf16_t, false>), dim3(g), dim3(256), 0, st, a, (const bf16_t*)logits, canvas, classes);
+    FS_DTYPE_SWITCH(d->dtype, T, FS_LAUNCH((eval_score_kernel<T, false>), dim3(g), dim3(256), 0, st, a, (const T*)logits, canvas, classes));
     return check_launch("fs_eval_score_accumulate");
 }
 

@@ -235,7 +235,7 @@ fs_status st = FS_OK;
             break;
         case FS_OP_STEM_U8:
             NEED(18);
-            st = fs_conv_stem_u8_fwd(stream, I(0), I(1), I(2), I(3), (const unsigned char*)P(4), PF(5), PF(6), PF(7), P(8), I(9), I(10), I(11),
+            st = fs_conv_stem_u8_infer_fwd(stream, I(0), I(1), I(2), I(3), (const unsigned char*)P(4), PF(5), PF(6), PF(7), P(8), I(9), I(10), I(11),
                                      F(12), F(13), F(14), F(15), F(16), F(17));
             break;
         case FS_OP_COPY_CHANNELS:

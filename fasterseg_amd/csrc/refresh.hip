@@ -20,7 +20,7 @@ constexpr int REFRESH_CHUNK = 4096;       // destination elements per block
 // destination elements of an entry (host: validated entries only)
 __host__ __device__ inline long long refresh_elems(const fs_refresh_entry& e) {
     if (e.kind == FS_REFRESH_PACK) return (long long)e.Cout * e.R * e.S * e.Cin;
-    if (e.kind == FS_REFRESH_PACK_FRAG) return pack_frag_elems(e.Cout, e.Cin, e.dtype == FS_BF16 ? 8 : 4);
+    if (e.kind == FS_REFRESH_PACK_FRAG) return pack_frag_elems(e.Cout, e.Cin, e.dtype == FS_F32 ? 4 : 8);      // elements per 16 bytes
     return e.Cout;
 }
 
@@ -55,10 +55,12 @@ __global__ __launch_bounds__(256) void refresh_weights_kernel(const fs_refresh_e
     switch (e.kind) {
         case FS_REFRESH_PACK:
             if (e.dtype == FS_BF16) refresh_pack<bf16_t>(e, begin, end);
+            else if (e.dtype == FS_F16) refresh_pack<f16_t>(e, begin, end);
             else refresh_pack<float>(e, begin, end);
             break;
         case FS_REFRESH_PACK_FRAG:
             if (e.dtype == FS_BF16) refresh_pack_frag<bf16_t>(e, begin, end);
+            else if (e.dtype == FS_F16) refresh_pack_frag<f16_t>(e, begin, end);
             else refresh_pack_frag<float>(e, begin, end);
             break;
         case FS_REFRESH_FOLD: {
@@ -84,14 +86,14 @@ using namespace fs;
 
 extern "C" int fs_refresh_chunk_elems(void) { return REFRESH_CHUNK; }
 
-extern "C" long long fs_refresh_entry_chunks(const fs_refresh_entry* e) {
+static long long entry_chunks(const fs_refresh_entry* e, bool f16_too) {
     FS_REQUIRE(e, -1, "fs_refresh_entry_chunks: null entry");
     FS_REQUIRE(e->kind >= FS_REFRESH_PACK && e->kind <= FS_REFRESH_BIAS, -1, "fs_refresh_entry_chunks: unknown kind %d", e->kind);
     FS_REQUIRE(e->Cout >= 1, -1, "fs_refresh_entry_chunks: Cout %d < 1", e->Cout);
     FS_REQUIRE(e->src, -1, "fs_refresh_entry_chunks: null source");
     if (e->kind == FS_REFRESH_PACK || e->kind == FS_REFRESH_PACK_FRAG) {
         FS_REQUIRE(e->Cin >= 1, -1, "fs_refresh_entry_chunks: Cin %d < 1", e->Cin);
-        FS_REQUIRE(e->dtype == FS_F32 || e->dtype == FS_BF16, -1, "fs_refresh_entry_chunks: bad dtype %d", e->dtype);
+        FS_REQUIRE(f16_too ? dtype_ok(e->dtype) : dtype_train_ok(e->dtype), -1, "fs_refresh_entry_chunks: bad dtype %d", e->dtype);
         FS_REQUIRE(e->R >= 1 && e->S >= 1, -1, "fs_refresh_entry_chunks: bad taps %dx%d", e->R, e->S);
         FS_REQUIRE(e->kind != FS_REFRESH_PACK_FRAG || (e->R == 3 && e->S == 3), -1,
                    "fs_refresh_entry_chunks: the fragment pack is 3x3 only (got %dx%d)", e->R, e->S);
@@ -106,6 +108,11 @@ extern "C" long long fs_refresh_entry_chunks(const fs_refresh_entry* e) {
     }
     return (refresh_elems(*e) + REFRESH_CHUNK - 1) / REFRESH_CHUNK;
 }
+
+// the validator of ABI 218: packs into fp32 / bf16, as its boundary contract says (any other code, FS_F16 included, is a bad dtype)
+extern "C" long long fs_refresh_entry_chunks(const fs_refresh_entry* e) { return entry_chunks(e, false); }
+// the same validator for an inference engine's table: packs into the three storage types
+extern "C" long long fs_refresh_entry_chunks_infer(const fs_refresh_entry* e) { return entry_chunks(e, true); }
 
 extern "C" fs_status fs_refresh_weights(void* stream, const fs_refresh_entry* entries, int n_entries, const int* chunks, int n_chunks) {
     FS_REQUIRE(entries && chunks, FS_ERR_INVALID, "fs_refresh_weights: null table");

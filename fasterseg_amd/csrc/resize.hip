@@ -83,6 +83,9 @@ template <> struct Quad<bf16_t> {
         o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
     }
 };
+template <> struct Quad<f16_t> {
+    static __device__ __forceinline__ void load(const f16_t* p, float* o) { f16_load4(p, o); }
+};
 template <typename TO> __device__ __forceinline__ void store4(TO* dst, const float* v);
 template <> __device__ __forceinline__ void store4<float>(float* dst, const float* v) {
     // the logits are written once and not read again by this graph: stream them past the caches
@@ -93,6 +96,10 @@ template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* dst, const fl
     o.x = (uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16);
     o.y = (uint32_t)f32_to_bf16(v[2]) | ((uint32_t)f32_to_bf16(v[3]) << 16);
     *reinterpret_cast<uint2*>(dst) = o;
+}
+
+template <> __device__ __forceinline__ void store4<f16_t>(f16_t* dst, const float* v) {
+    *reinterpret_cast<uint2*>(dst) = uint2{pack2_f16(v[0], v[1]), pack2_f16(v[2], v[3])};
 }
 
 template <typename T, typename TO>
@@ -461,11 +468,11 @@ static int g_logits_tiled = 1;
 /* test hook: 0 = the NCHW up-sample always takes the gather kernel (bilinear_fwd_nchw_kernel), never the tiled form */
 extern "C" void fs_debug_logits_tiled(int on) { g_logits_tiled = on; }
 
-static fs_status check_resize(const char* fn, const fs_resize_desc* d) {
+static fs_status check_resize(const char* fn, const fs_resize_desc* d, bool f16_too = false) {
     FS_REQUIRE(d, FS_ERR_INVALID, "%s: null descriptor", fn);
     FS_REQUIRE(d->N > 0 && d->Hi > 0 && d->Wi > 0 && d->Ho > 0 && d->Wo > 0 && d->C > 0, FS_ERR_INVALID,
                "%s: non-positive dimension", fn);
-    FS_REQUIRE(d->dtype == FS_F32 || d->dtype == FS_BF16, FS_ERR_INVALID, "%s: bad dtype", fn);
+    FS_REQUIRE(f16_too ? dtype_ok(d->dtype) : dtype_train_ok(d->dtype), FS_ERR_INVALID, "%s: bad dtype", fn);      // FS_F16: forward only
     if (!d->out_nchw) {
         const int vec = vec_elems(d->dtype);
         FS_REQUIRE(d->C % vec == 0 && d->x_cs % vec == 0 && d->y_cs % vec == 0 && d->x_cs >= d->C && d->y_cs >= d->C,
@@ -480,7 +487,7 @@ static fs_status check_resize(const char* fn, const fs_resize_desc* d) {
 }
 
 extern "C" fs_status fs_bilinear_fwd(void* stream, const fs_resize_desc* d, const void* x, void* y) {
-    fs_status s = check_resize("fs_bilinear_fwd", d);
+    fs_status s = check_resize("fs_bilinear_fwd", d, true);
     if (s != FS_OK) return s;
     FS_REQUIRE(x && y, FS_ERR_INVALID, "fs_bilinear_fwd: null pointer");
     const float rh = host_scale(d->Hi, d->Ho), rw = host_scale(d->Wi, d->Wo);
@@ -491,8 +498,7 @@ extern "C" fs_status fs_bilinear_fwd(void* stream, const fs_resize_desc* d, cons
         const long long total = (long long)d->N * d->Ho * d->Wo * cv;
         const ResizeArgs q{d->N, d->Hi, d->Wi, d->Ho, d->Wo, cv, rh, rw, x, d->x_cs, nullptr, 0, y, d->y_cs, d->relu};
         FS_NOTE_BYTES((double)d->N * d->C * elem_size(d->dtype) * ((double)d->Hi * d->Wi + (double)d->Ho * d->Wo));
-        if (d->dtype == FS_F32) FS_LAUNCH((bilinear_fwd_kernel<float>), dim3(grid_for(total)), dim3(256), 0, st, q);
-        else FS_LAUNCH((bilinear_fwd_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, st, q);
+        FS_DTYPE_SWITCH(d->dtype, T, FS_LAUNCH((bilinear_fwd_kernel<T>), dim3(grid_for(total)), dim3(256), 0, st, q));
     } else {
         const bool out_f32 = (d->out_nchw == 1) || d->dtype == FS_F32;
         // tiled form: the staged window of a tile must fit its LDS budget (any up-sample by ~x4 or more at 19 classes; a down-sample or a
@@ -502,39 +508,27 @@ extern "C" fs_status fs_bilinear_fwd(void* stream, const fs_resize_desc* d, cons
             d->Wi < 32768) {
             const dim3 g((unsigned)((d->Wo + LT_TW - 1) / LT_TW), (unsigned)((d->Ho + LT_TR - 1) / LT_TR), (unsigned)d->N);
             const size_t lds = (size_t)lt_bytes;
-            if (d->dtype == FS_F32)
-                FS_LAUNCH((bilinear_fwd_nchw_tiled_kernel<float, float>), g, dim3(256), lds, st, d->Hi, d->Wi, d->Ho, d->Wo, d->C, rh, rw,
-                                   (const float*)x, d->x_cs, (float*)y);
-            else if (out_f32)
-                FS_LAUNCH((bilinear_fwd_nchw_tiled_kernel<bf16_t, float>), g, dim3(256), lds, st, d->Hi, d->Wi, d->Ho, d->Wo, d->C, rh, rw,
-                                   (const bf16_t*)x, d->x_cs, (float*)y);
-            else
-                FS_LAUNCH((bilinear_fwd_nchw_tiled_kernel<bf16_t, bf16_t>), g, dim3(256), lds, st, d->Hi, d->Wi, d->Ho, d->Wo, d->C, rh,
-                                   rw, (const bf16_t*)x, d->x_cs, (bf16_t*)y);
+            // input T, output fp32 (out_nchw == 1, or fp32 storage) or T
+            FS_DTYPE_SWITCH(d->dtype, T, {
+                if (out_f32) FS_LAUNCH((bilinear_fwd_nchw_tiled_kernel<T, float>), g, dim3(256), lds, st, d->Hi, d->Wi, d->Ho, d->Wo, d->C, rh, rw, (const T*)x, d->x_cs, (float*)y);
+                else FS_LAUNCH((bilinear_fwd_nchw_tiled_kernel<T, T>), g, dim3(256), lds, st, d->Hi, d->Wi, d->Ho, d->Wo, d->C, rh, rw, (const T*)x, d->x_cs, (T*)y);
+            });
         } else if (d->Wo % 4 == 0) {
             const long long total = (long long)d->N * ((d->C + 3) / 4) * d->Ho * (d->Wo / 4);
             const dim3 g(grid_for(total));
-            if (d->dtype == FS_F32)
-                FS_LAUNCH((bilinear_fwd_nchw_kernel<float, float>), g, dim3(256), 0, st, d->N, d->Hi, d->Wi, d->Ho, d->Wo,
-                                   d->C, rh, rw, (const float*)x, d->x_cs, (float*)y);
-            else if (out_f32)
-                FS_LAUNCH((bilinear_fwd_nchw_kernel<bf16_t, float>), g, dim3(256), 0, st, d->N, d->Hi, d->Wi, d->Ho, d->Wo,
-                                   d->C, rh, rw, (const bf16_t*)x, d->x_cs, (float*)y);
-            else
-                FS_LAUNCH((bilinear_fwd_nchw_kernel<bf16_t, bf16_t>), g, dim3(256), 0, st, d->N, d->Hi, d->Wi, d->Ho,
-                                   d->Wo, d->C, rh, rw, (const bf16_t*)x, d->x_cs, (bf16_t*)y);
+            // input T, output fp32 (out_nchw == 1, or fp32 storage) or T
+            FS_DTYPE_SWITCH(d->dtype, T, {
+                if (out_f32) FS_LAUNCH((bilinear_fwd_nchw_kernel<T, float>), g, dim3(256), 0, st, d->N, d->Hi, d->Wi, d->Ho, d->Wo, d->C, rh, rw, (const T*)x, d->x_cs, (float*)y);
+                else FS_LAUNCH((bilinear_fwd_nchw_kernel<T, T>), g, dim3(256), 0, st, d->N, d->Hi, d->Wi, d->Ho, d->Wo, d->C, rh, rw, (const T*)x, d->x_cs, (T*)y);
+            });
         } else {
             const long long total = (long long)d->N * d->C * d->Ho * d->Wo;
             const dim3 g(grid_for(total));
-            if (d->dtype == FS_F32)
-                FS_LAUNCH((bilinear_fwd_nchw_scalar_kernel<float, float>), g, dim3(256), 0, st, d->N, d->Hi, d->Wi, d->Ho,
-                                   d->Wo, d->C, rh, rw, (const float*)x, d->x_cs, (float*)y);
-            else if (out_f32)
-                FS_LAUNCH((bilinear_fwd_nchw_scalar_kernel<bf16_t, float>), g, dim3(256), 0, st, d->N, d->Hi, d->Wi, d->Ho,
-                                   d->Wo, d->C, rh, rw, (const bf16_t*)x, d->x_cs, (float*)y);
-            else
-                FS_LAUNCH((bilinear_fwd_nchw_scalar_kernel<bf16_t, bf16_t>), g, dim3(256), 0, st, d->N, d->Hi, d->Wi,
-                                   d->Ho, d->Wo, d->C, rh, rw, (const bf16_t*)x, d->x_cs, (bf16_t*)y);
+            // input T, output fp32 (out_nchw == 1, or fp32 storage) or T
+            FS_DTYPE_SWITCH(d->dtype, T, {
+                if (out_f32) FS_LAUNCH((bilinear_fwd_nchw_scalar_kernel<T, float>), g, dim3(256), 0, st, d->N, d->Hi, d->Wi, d->Ho, d->Wo, d->C, rh, rw, (const T*)x, d->x_cs, (float*)y);
+                else FS_LAUNCH((bilinear_fwd_nchw_scalar_kernel<T, T>), g, dim3(256), 0, st, d->N, d->Hi, d->Wi, d->Ho, d->Wo, d->C, rh, rw, (const T*)x, d->x_cs, (T*)y);
+            });
         }
     }
     return check_launch("fs_bilinear_fwd");
@@ -603,7 +597,7 @@ static fs_status bilinear_any_group(void* stream, const ResizeCall* c, int n, bo
         for (int j = 0; j < m; ++j) {
             const ResizeCall& q = c[sub[j]];
             const fs_resize_desc* d = q.d;
-            const fs_status s = check_resize(fn, d);
+            const fs_status s = check_resize(fn, d, !backward);
             if (s != FS_OK) return s;
             FS_REQUIRE(q.a && q.out && aligned16(q.a) && aligned16(q.out), FS_ERR_INVALID, "%s: operands must be non-null and 16-byte aligned", fn);
             FS_REQUIRE(!backward || !d->relu || q.b, FS_ERR_INVALID, "fs_bilinear_bwd: relu backward needs y_out");
@@ -622,8 +616,7 @@ static fs_status bilinear_any_group(void* stream, const ResizeCall* c, int n, bo
             if (f32) FS_LAUNCH((bilinear_bwd_group_kernel<float>), dim3(grid), dim3(256), 0, st, g);
             else FS_LAUNCH((bilinear_bwd_group_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, g);
         } else {
-            if (f32) FS_LAUNCH((bilinear_fwd_group_kernel<float>), dim3(grid), dim3(256), 0, st, g);
-            else FS_LAUNCH((bilinear_fwd_group_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, g);
+            FS_DTYPE_SWITCH(c[sub[0]].d->dtype, T, FS_LAUNCH((bilinear_fwd_group_kernel<T>), dim3(grid), dim3(256), 0, st, g));
         }
         return check_launch(fn);
     });

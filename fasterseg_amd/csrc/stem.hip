@@ -306,12 +306,13 @@ __device__ __forceinline__ void stem_tile_origin(int t, int tyn, int txn, int& n
     ow0 = (u - n * txn) * S_TW;
 }
 
-template <typename Src, int NT>                              // n-tiles of 32 output channels: 1 (Cout <= 32) or 2
+template <typename Src, int NT, typename TO>                 // n-tiles of 32 output channels: 1 (Cout <= 32) or 2; TO: bf16_t or f16_t output
 __global__ __launch_bounds__(256, NT == 1 ? 4 : 3) void stem_mfma_kernel(int N, int H, int W, int Ho, int Wo, int Cout,
                                                         const typename Src::Elem* __restrict__ x,
                                                         const float* __restrict__ w, const float* __restrict__ scale,
-                                                        const float* __restrict__ shift, bf16_t* __restrict__ y, int y_cs, int relu,
+                                                        const float* __restrict__ shift, TO* __restrict__ y, int y_cs, int relu,
                                                         typename Src::Norm nm) {
+    static_assert(sizeof(TO) == 2, "16-bit output");
     constexpr int OUT_PITCH = 32 * 2 + 16;                   // bytes per pixel row of the transpose tile
     __shared__ __attribute__((aligned(16))) float win[2][S_WIN + 4];     // two window buffers, each + a zero word for the K padding
     __shared__ __attribute__((aligned(16))) unsigned char sout[4][32 * OUT_PITCH];
@@ -392,7 +393,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 4 : 3) void stem_mfma_kernel(int N, 
                     const int prow = (r & 3) + 8 * (r >> 2) + 4 * half;               // pixel (column) of the m-tile
                     float o = acc[r] * sc + sh;
                     if (relu) o = fmaxf(o, 0.f);
-                    *reinterpret_cast<bf16_t*>(so + prow * OUT_PITCH + l31 * 2) = f32_to_bf16(o);
+                    Elem<TO>::store(reinterpret_cast<TO*>(so + prow * OUT_PITCH + l31 * 2), o);
                 }
                 __builtin_amdgcn_wave_barrier();
                 const int cbase = nt * 32;
@@ -440,43 +441,35 @@ static fs_status stem_launch(const char* name, void* stream, int N, int H, int W
                              const float* scale, const float* shift, void* y, int y_cs, int dtype, int relu, typename Src::Norm nm) {
     FS_REQUIRE(x && w && y, FS_ERR_INVALID, "%s: null pointer", name);
     FS_REQUIRE(N > 0 && H > 1 && W > 1 && Cout > 0, FS_ERR_INVALID, "%s: bad shape", name);
-    FS_REQUIRE(dtype == FS_F32 || dtype == FS_BF16, FS_ERR_INVALID, "%s: bad dtype", name);
+    FS_REQUIRE(dtype_ok(dtype), FS_ERR_INVALID, "%s: bad dtype", name);
     FS_REQUIRE(y_cs >= Cout && y_cs % vec_elems(dtype) == 0 && aligned16(y), FS_ERR_INVALID,
                "%s: output slice misaligned (y_cs=%d)", name, y_cs);
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     if (W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & (Src::ALIGN - 1)) == 0 && N <= 65535) {   // LDS-tiled kernels: coalesced quad loads
         dim3 tiles((unsigned)((Wo + S_TW - 1) / S_TW), (unsigned)((Ho + S_TH - 1) / S_TH), (unsigned)N);
         const long long ntile = (long long)tiles.x * tiles.y * tiles.z;
-        if (dtype == FS_BF16 && Cout <= 64 && Cout % 8 == 0 && g_stem_mfma && ntile < (1ll << 31)) {      // matrix-core form (split-bf16 operands)
+        if (elem_size(dtype) == 2 && Cout <= 64 && Cout % 8 == 0 && g_stem_mfma && ntile < (1ll << 31)) {      // matrix-core form (split-bf16 operands, bf16 or fp16 store)
             // resident blocks per compute unit: 4 x 39.6 KB of LDS at one n-tile; two n-tiles hold twice the filter fragments (3 by registers)
             long long blocks = g_stem_blocks > 0 ? g_stem_blocks : (long long)(Cout <= 32 ? 4 : 3) * compute_units();
             if (blocks > ntile) blocks = ntile;
             if (Cout <= 32)
-                FS_LAUNCH((stem_mfma_kernel<Src, 1>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, N, H, W, Ho, Wo, Cout, x, w,
-                                   scale, shift, (bf16_t*)y, y_cs, relu, nm);
+                FS_DTYPE16_SWITCH(dtype, T, FS_LAUNCH((stem_mfma_kernel<Src, 1, T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, N, H, W,
+                                                      Ho, Wo, Cout, x, w, scale, shift, (T*)y, y_cs, relu, nm));
             else
-                FS_LAUNCH((stem_mfma_kernel<Src, 2>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, N, H, W, Ho, Wo, Cout, x, w,
-                                   scale, shift, (bf16_t*)y, y_cs, relu, nm);
+                FS_DTYPE16_SWITCH(dtype, T, FS_LAUNCH((stem_mfma_kernel<Src, 2, T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, N, H, W,
+                                                      Ho, Wo, Cout, x, w, scale, shift, (T*)y, y_cs, relu, nm));
             return check_launch(name);
         }
-        if (dtype == FS_F32)
-            FS_LAUNCH((stem_lds_kernel<Src, float>), tiles, dim3(256), 0, (hipStream_t)stream, H, W, Ho, Wo, Cout, x, w, scale,
-                               shift, (float*)y, y_cs, relu, nm);
-        else
-            FS_LAUNCH((stem_lds_kernel<Src, bf16_t>), tiles, dim3(256), 0, (hipStream_t)stream, H, W, Ho, Wo, Cout, x, w, scale,
-                               shift, (bf16_t*)y, y_cs, relu, nm);
+        FS_DTYPE_SWITCH(dtype, T, FS_LAUNCH((stem_lds_kernel<Src, T>), tiles, dim3(256), 0, (hipStream_t)stream, H, W, Ho, Wo, Cout, x, w, scale,
+                                            shift, (T*)y, y_cs, relu, nm));
         return check_launch(name);
     }
     const long long total = (long long)N * Ho * Wo;
     long long gx = (total + 255) / 256;
     if (gx > 32768) gx = 32768;
     dim3 grid((unsigned)gx, (Cout + 15) / 16);
-    if (dtype == FS_F32)
-        FS_LAUNCH((stem_conv_kernel<Src, float>), grid, dim3(256), 0, (hipStream_t)stream, N, H, W, Ho, Wo, Cout, x, w, scale,
-                           shift, (float*)y, y_cs, relu, nm);
-    else
-        FS_LAUNCH((stem_conv_kernel<Src, bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, N, H, W, Ho, Wo, Cout, x, w, scale,
-                           shift, (bf16_t*)y, y_cs, relu, nm);
+    FS_DTYPE_SWITCH(dtype, T, FS_LAUNCH((stem_conv_kernel<Src, T>), grid, dim3(256), 0, (hipStream_t)stream, N, H, W, Ho, Wo, Cout, x, w, scale,
+                                        shift, (T*)y, y_cs, relu, nm));
     return check_launch(name);
 }
 
@@ -485,11 +478,31 @@ extern "C" fs_status fs_conv_stem_fwd(void* stream, int N, int H, int W, int Cou
     return stem_launch<StemF32>("fs_conv_stem_fwd", stream, N, H, W, Cout, x, w, scale, shift, y, y_cs, dtype, relu, StemNoNorm{});
 }
 
+static fs_status stem_u8(const char* name, void* stream, int N, int H, int W, int Cout, const unsigned char* img, const float* w,
+                         const float* scale, const float* shift, void* y, int y_cs, int dtype, int relu, float mean_r, float mean_g,
+                         float mean_b, float std_r, float std_g, float std_b) {
+    FS_REQUIRE(std_r != 0.f && std_g != 0.f && std_b != 0.f, FS_ERR_INVALID, "%s: std must be non-zero (%g, %g, %g)", name,
+               (double)std_r, (double)std_g, (double)std_b);
+    const StemNorm nm = {{mean_r, mean_g, mean_b}, {std_r, std_g, std_b}};
+    return stem_launch<StemU8>(name, stream, N, H, W, Cout, img, w, scale, shift, y, y_cs, dtype, relu, nm);
+}
+
+// the entry point of ABI 221: fp32 / bf16, as its boundary contract says (any other code, FS_F16 included, is "bad dtype")
 extern "C" fs_status fs_conv_stem_u8_fwd(void* stream, int N, int H, int W, int Cout, const unsigned char* img, const float* w,
                                          const float* scale, const float* shift, void* y, int y_cs, int dtype, int relu,
                                          float mean_r, float mean_g, float mean_b, float std_r, float std_g, float std_b) {
     FS_REQUIRE(std_r != 0.f && std_g != 0.f && std_b != 0.f, FS_ERR_INVALID, "fs_conv_stem_u8_fwd: std must be non-zero (%g, %g, %g)",
                (double)std_r, (double)std_g, (double)std_b);
-    const StemNorm nm = {{mean_r, mean_g, mean_b}, {std_r, std_g, std_b}};
-    return stem_launch<StemU8>("fs_conv_stem_u8_fwd", stream, N, H, W, Cout, img, w, scale, shift, y, y_cs, dtype, relu, nm);
+    // (null pointers and bad shapes keep their messages, which come first)
+    FS_REQUIRE(!(img && w && y && N > 0 && H > 1 && W > 1 && Cout > 0) || dtype_train_ok(dtype), FS_ERR_INVALID, "fs_conv_stem_u8_fwd: bad dtype");
+    return stem_u8("fs_conv_stem_u8_fwd", stream, N, H, W, Cout, img, w, scale, shift, y, y_cs, dtype, relu, mean_r, mean_g, mean_b, std_r,
+                   std_g, std_b);
+}
+
+// the same launch for the three storage types: what an inference engine and the program executor issue
+extern "C" fs_status fs_conv_stem_u8_infer_fwd(void* stream, int N, int H, int W, int Cout, const unsigned char* img, const float* w,
+                                               const float* scale, const float* shift, void* y, int y_cs, int dtype, int relu,
+                                               float mean_r, float mean_g, float mean_b, float std_r, float std_g, float std_b) {
+    return stem_u8("fs_conv_stem_u8_infer_fwd", stream, N, H, W, Cout, img, w, scale, shift, y, y_cs, dtype, relu, mean_r, mean_g, mean_b,
+                   std_r, std_g, std_b);
 }

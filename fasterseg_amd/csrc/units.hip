@@ -24,7 +24,7 @@ static const long long BN_COL_MAX_PIXELS = 512;
 // launches of its unit table - stats_in_epilogue() and UnitProblem.mode there: retune them together, and keep units on both sides)
 static bool stats_in_epilogue(long long M, int C, int dtype) {
     const double epilogue_us = (double)M / 32 * 0.02;
-    const double pass_us = 8.0 + (double)M * C * (dtype == FS_F32 ? 4 : 2) / 3.0e6;
+    const double pass_us = 8.0 + (double)M * C * fs::elem_size(dtype) / 3.0e6;
     return epilogue_us <= pass_us;
 }
 
@@ -81,6 +81,7 @@ extern "C" fs_status fs_conv_bn_act_train_fwd(void* stream, const fs_conv_desc* 
                                               float momentum, float* stats, float* saved, void* z, void* y, void* workspace,
                                               long long workspace_bytes) {
     FS_REQUIRE(d && x && w_packed && stats && saved && z && y, FS_ERR_INVALID, "fs_conv_bn_act_train_fwd: null argument");
+    FS_REQUIRE(fs::dtype_train_ok(d->dtype), FS_ERR_INVALID, "fs_conv_bn_act_train_fwd: bad dtype %d (training is fp32 / bf16)", d->dtype);
     fs_conv_desc c = *d;
     c.flags &= ~(FS_CONV_RELU | FS_CONV_RELU_TAIL);          // the conv writes the raw pre-normalisation map z
     c.k_seg = c.k_jump = 0;            // (k_jump of a fused unit describes the rotated pack of its backward)
@@ -118,6 +119,7 @@ extern "C" fs_status fs_conv_bn_act_train_bwd(void* stream, const fs_conv_desc* 
                                               long long t_stride, void* dx, int dx_cs, int wf_os, int wf_ts, void* workspace,
                                               long long workspace_bytes) {
     FS_REQUIRE(d && z && dy && saved && gamma && red && dz, FS_ERR_INVALID, "fs_conv_bn_act_train_bwd: null argument");
+    FS_REQUIRE(fs::dtype_train_ok(d->dtype), FS_ERR_INVALID, "fs_conv_bn_act_train_bwd: bad dtype %d (training is fp32 / bf16)", d->dtype);
     const int relu = unit_relu(d);
     FS_REQUIRE(!relu || y, FS_ERR_INVALID, "fs_conv_bn_act_train_bwd: ReLU unit needs its output y");
     const int C = d->Cout;
@@ -280,6 +282,8 @@ fs_status fs::bn_bwd_group(void* stream, const BnBwdCall* c, int n) {
 // single-unit entry points above except that no convolution is split over K (a group fills the chip without it).
 fs_status fs::unit_fwd_group(void* stream, const UnitFwdCall* u, int n) {
     FS_REQUIRE(n >= 1 && n <= FS_MAX_GROUP, FS_ERR_INVALID, "unit_fwd_group: %d units", n);
+    for (int i = 0; i < n; ++i)
+        FS_REQUIRE(u[i].d && fs::dtype_train_ok(u[i].d->dtype), FS_ERR_INVALID, "unit_fwd_group: bad dtype (training is fp32 / bf16)");
     fs_conv_desc c[FS_MAX_GROUP];
     const fs_conv_desc* cp[FS_MAX_GROUP];
     ConvArgs args[FS_MAX_GROUP];
@@ -318,6 +322,8 @@ fs_status fs::unit_fwd_group(void* stream, const UnitFwdCall* u, int n) {
 
 fs_status fs::unit_bwd_group(void* stream, const UnitBwdCall* u, int n, WgradSink* sink) {
     FS_REQUIRE(n >= 1 && n <= FS_MAX_GROUP, FS_ERR_INVALID, "unit_bwd_group: %d units", n);
+    for (int i = 0; i < n; ++i)
+        FS_REQUIRE(u[i].d && fs::dtype_train_ok(u[i].d->dtype), FS_ERR_INVALID, "unit_bwd_group: bad dtype (training is fp32 / bf16)");
     fs_status s;
     // 1. BatchNorm backward of every unit (dz): one launch per step of the sequence for all units (bn_bwd_group)
     {

@@ -456,6 +456,10 @@ template <typename T, int NT> static void launch_zoom(hipStream_t st, const Zoom
     FS_LAUNCH((zoom_cell_kernel<T, NT>), dim3((unsigned)blocks), dim3(256), 0, st, a);
 }
 
+template <int NT> static void launch_zoom16(hipStream_t st, ZoomArgs& a, int dtype) {          // the two 16-bit storage types
+    FS_DTYPE16_SWITCH(dtype, T, launch_zoom<T, NT>(st, a));
+}
+
 static inline float zoom_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
 }  // namespace fs
@@ -464,12 +468,12 @@ using namespace fs;
 
 extern "C" int fs_zoom_cell_supported(const fs_zoom_desc* d) {
     if (!d) return 0;
-    if (d->dtype != FS_F32 && d->dtype != FS_BF16) return 0;
+    if (!dtype_ok(d->dtype)) return 0;
     const int vec = vec_elems(d->dtype);
     if (d->Cin <= 0 || d->Cin % vec || d->Cmid % vec || d->Cout % vec || d->x_cs % vec || d->y_cs % vec) return 0;
     if (d->Cmid != d->Cout) return 0;
     const int nt = (d->Cmid + 31) / 32;
-    const int nt_max = d->dtype == FS_BF16 ? 8 : 4;             // LDS: all mid channels of R1 stay resident
+    const int nt_max = 16 / elem_size(d->dtype);                // LDS: all mid channels of R1 stay resident
     if (nt > nt_max) return 0;
     if (d->down ? (d->H % 2 || d->W % 2 || d->h != d->H / 2 || d->w != d->W / 2 || d->h < 2 || d->w < 2) : (d->h != d->H || d->w != d->W)) return 0;
     if (d->up ? (d->Ho != 2 * d->h || d->Wo != 2 * d->w) : (d->Ho != d->h || d->Wo != d->w)) return 0;
@@ -501,15 +505,15 @@ extern "C" fs_status fs_zoom_cell_fwd(void* stream, const fs_zoom_desc* d, const
     a.rh_up = zoom_scale(a.h, a.Ho); a.rw_up = zoom_scale(a.w, a.Wo);
     const int nt = (a.Cmid + 31) / 32;
     hipStream_t st = (hipStream_t)stream;
-    if (d->dtype == FS_BF16) {
+    if (elem_size(d->dtype) == 2) {
         switch (nt) {
-            case 1: launch_zoom<bf16_t, 1>(st, a); break;
-            case 2: launch_zoom<bf16_t, 2>(st, a); break;
-            case 3: launch_zoom<bf16_t, 3>(st, a); break;
-            case 4: launch_zoom<bf16_t, 4>(st, a); break;
+            case 1: launch_zoom16<1>(st, a, d->dtype); break;
+            case 2: launch_zoom16<2>(st, a, d->dtype); break;
+            case 3: launch_zoom16<3>(st, a, d->dtype); break;
+            case 4: launch_zoom16<4>(st, a, d->dtype); break;
             case 5:
-            case 6: launch_zoom<bf16_t, 6>(st, a); break;      // filter banks are zero-filled up to whole 128-channel tiles
-            default: launch_zoom<bf16_t, 8>(st, a); break;
+            case 6: launch_zoom16<6>(st, a, d->dtype); break;      // filter banks are zero-filled up to whole 128-channel tiles
+            default: launch_zoom16<8>(st, a, d->dtype); break;
         }
     } else {
         switch (nt) {

@@ -84,6 +84,9 @@ class InferenceEngine:
                 raise ValueError("image_mean / image_std: three values each, std non-zero")
             if len(input_shape) != 4 or input_shape[1] != 3:
                 raise ValueError("input='uint8' needs input_shape (N, 3, H, W), got %r" % (tuple(input_shape),))
+        K.dtype_code(dtype)
+        if logits_dtype not in (torch.float32, dtype):
+            raise ValueError("logits_dtype must be torch.float32 or the engine dtype %s, got %s" % (dtype, logits_dtype))
         self.dtype = dtype
         self.device = torch.device(device)
         self.input_shape = tuple(input_shape)
@@ -136,7 +139,7 @@ class InferenceEngine:
             import json
             sig = hashlib.sha1(repr((tuple(self.input_shape), [(op["kind"], tuple(op["out"].shape)) for op in self.ops])).encode()).hexdigest()[:12]
             self._plan_out["signature"] = sig
-            self._plan_path = "%s.%s.%s.%s" % (self._plan_path, output, "bf16" if dtype == torch.bfloat16 else "fp32", sig)
+            self._plan_path = "%s.%s.%s.%s" % (self._plan_path, output, K.DTYPE_NAMES[dtype], sig)
             if os.path.exists(self._plan_path):
                 with open(self._plan_path) as f:
                     plan = json.load(f)
@@ -373,10 +376,10 @@ class InferenceEngine:
     def _mark_head_fusions(self):
         """`3x3 -> 1x1` chains whose intermediate map has exactly one consumer and is not the engine's output (head_fusion.match).
         Candidates only: `_lower` builds the fused launch (fs_conv3x3_pw_fwd) beside the separate
-        launches and `_tune_cells` keeps it where the frame gets faster.  bf16 only: the fp32 engine keeps the separate launches."""
+        launches and `_tune_cells` keeps it where the frame gets faster.  16-bit storage types only: the fp32 engine keeps the separate launches."""
         from . import head_fusion
         self.head_matches = []
-        if getattr(self, "fuse_head", 1) and getattr(self, "dtype", torch.bfloat16) == torch.bfloat16:
+        if getattr(self, "fuse_head", 1) and K.elem_size(getattr(self, "dtype", torch.bfloat16)) == 2:
             self.head_matches = head_fusion.match(self.ops, self.out_sym)
         for m in self.head_matches:
             self.ops[m["post"]]["head"] = m
@@ -478,7 +481,7 @@ class InferenceEngine:
         use_halo = halo_ok and stride == 1 and (N * H * W >= self.halo_min_pixels or vres_halo)
         xp, x_cs = self._ptr(x)
         yp, y_cs = self._ptr(out)
-        yp += out_off * (2 if self.dtype == torch.bfloat16 else 4)
+        yp += out_off * K.elem_size(self.dtype)
         d = ConvDesc(N, H, W, cin, cout, k, k, stride, pad, Ho, Wo, x_cs, y_cs, K.dtype_code(self.dtype), FS_CONV_RELU if relu else 0)
         if vres is not None:
             d.vr_H, d.vr_W, d.vr_relu = src_hw[0], src_hw[1], int(vres[2])
@@ -522,7 +525,7 @@ class InferenceEngine:
             fn, args, wp, dsel = best[2]
         self._keep.append(wp)
         self._record(_lib.FS_REFRESH_PACK_FRAG if fn == "fs_conv3x3_s1_fwd" else _lib.FS_REFRESH_PACK, weight, wp, cout=cout, cin=cin, dtype=self.dtype)
-        es = 2 if self.dtype == torch.bfloat16 else 4
+        es = K.elem_size(self.dtype)
         flops = 2.0 * N * Ho * Wo * cout * cin * k * k
         in_px = N * (src_hw[0] * src_hw[1] if src_hw else H * W)
         nbytes = es * (in_px * cin + cout * cin * k * k + N * Ho * Wo * cout)
@@ -547,7 +550,7 @@ class InferenceEngine:
         return sym
 
     def _resize_call(self, x, out, relu):
-        es = 2 if self.dtype == torch.bfloat16 else 4
+        es = K.elem_size(self.dtype)
         N, C, Hi, Wi = x.shape
         Ho, Wo = out.shape[2], out.shape[3]
         xp, x_cs = self._ptr(x)
@@ -587,7 +590,7 @@ class InferenceEngine:
 
     def _add_zoom(self, op, out):
         A, B, x, down, up = op["A"], op["B"], op["x"], op["down"], op["up"]
-        es = 2 if self.dtype == torch.bfloat16 else 4
+        es = K.elem_size(self.dtype)
         N, _, H, W = x.shape
         cin, cmid, cout = A["cin"], A["cout"], B["cout"]
         xp, x_cs = self._ptr(x)
@@ -679,7 +682,7 @@ class InferenceEngine:
         """Ops -> call groups (a group = the launches of one op; a cell has two alternative groups), then _flatten()."""
         self.calls = []
         self.groups = []
-        es = 2 if self.dtype == torch.bfloat16 else 4
+        es = K.elem_size(self.dtype)
         for idx, op in enumerate(self.ops):
             if op.get("dead"):
                 continue
@@ -699,7 +702,8 @@ class InferenceEngine:
                         ctypes.c_void_p(yp), y_cs, K.dtype_code(self.dtype), int(op["relu"]))
                 Ho, Wo = out.shape[2], out.shape[3]
                 if self.input_mode == "uint8":           # the same launch on the uint8 frame: 3 bytes per pixel in, normalised in the stem
-                    self.calls.append(dict(fn="fs_conv_stem_u8_fwd", args=args + self.image_mean + self.image_std, family="stem",
+                    # (fs_conv_stem_u8_fwd keeps its published fp32 / bf16 contract; fp16 takes the three-type entry point)
+                    self.calls.append(dict(fn="fs_conv_stem_u8_infer_fwd" if self.dtype == torch.float16 else "fs_conv_stem_u8_fwd", args=args + self.image_mean + self.image_std, family="stem",
                                            flops=2.0 * N * Ho * Wo * cout * 27, bytes=N * H * W * 3 + es * N * Ho * Wo * cout,
                                            label="stem u8 3x3 s2 3->%d @%dx%d" % (cout, H, W)))
                 else:
@@ -1048,7 +1052,8 @@ class InferenceEngine:
         self._bind_sources()
         chunks, nbytes = [], 0
         for t, (e, r) in enumerate(zip(entries, self._refresh)):
-            c = lib.fs_refresh_entry_chunks(ctypes.byref(e))
+            # (fs_refresh_entry_chunks keeps its published fp32 / bf16 contract; an fp16 pack is validated by the three-type form)
+            c = (lib.fs_refresh_entry_chunks_infer if e.dtype == _lib.FS_F16 else lib.fs_refresh_entry_chunks)(ctypes.byref(e))
             if c < 0:
                 self._refresh_tab = None
                 raise _lib.FasterSegHipError("fs_refresh_entry_chunks: %s" % lib.fs_last_error().decode())
@@ -1145,7 +1150,7 @@ class InferenceEngine:
 
     # ---- 4b. the plan as one multi-stream launch program (fs_exec_program_streams) ---------------------------------
     _OPS = {"fs_bilinear_argmax": "OP_BILINEAR_ARGMAX", "fs_zoom_cell_fwd": "OP_ZOOM_CELL", "fs_conv2d_fwd_ws": "OP_CONV_FWD", "fs_conv2d_fwd": "OP_CONV_FWD", "fs_conv3x3_s1_fwd": "OP_CONV3X3_S1", "fs_conv3x3_pw_fwd": "OP_CONV3X3_PW",
-            "fs_conv_stem_fwd": "OP_STEM", "fs_conv_stem_u8_fwd": "OP_STEM_U8", "fs_bilinear_fwd": "OP_BILINEAR_FWD", "fs_copy_channels": "OP_COPY_CHANNELS"}
+            "fs_conv_stem_fwd": "OP_STEM", "fs_conv_stem_u8_fwd": "OP_STEM_U8", "fs_conv_stem_u8_infer_fwd": "OP_STEM_U8", "fs_bilinear_fwd": "OP_BILINEAR_FWD", "fs_copy_channels": "OP_COPY_CHANNELS"}
 
     def _build_program(self):
         """Same launches, lanes and cross-lane edges as `_launch_all_lanes`, as a relocatable-free command list (all

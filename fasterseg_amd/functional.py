@@ -42,9 +42,10 @@ class SymTensor:
 
 
 def set_compute_dtype(dtype):
-    """Storage/compute dtype used when an operator receives a plain NCHW fp32 tensor (float32 or bfloat16)."""
+    """Storage/compute dtype used when an operator receives a plain NCHW fp32 tensor (float32 or bfloat16; float16 is an
+    inference-engine storage type, the operators train and are refused it here)."""
     global _compute_dtype
-    K.dtype_code(dtype)
+    K.require_train_dtype(dtype, "set_compute_dtype")
     _compute_dtype = dtype
 
 

@@ -10,20 +10,39 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FS_BF16, FS_CONV_RELU, FS_CONV_RELU_TAIL, FS_CONV_TRANSPOSED, FS_F32, ConvDesc, ResizeDesc, ZoomDesc, call
+from ._lib import FS_BF16, FS_CONV_RELU, FS_CONV_RELU_TAIL, FS_CONV_TRANSPOSED, FS_F16, FS_F32, ConvDesc, ResizeDesc, ZoomDesc, call
 
-_DT = {torch.float32: FS_F32, torch.bfloat16: FS_BF16}
+_DT = {torch.float32: FS_F32, torch.bfloat16: FS_BF16, torch.float16: FS_F16}
+# what trains: float16 is an inference storage type (the C ABI refuses it in every training entry point)
+TRAIN_DTYPES = (torch.float32, torch.bfloat16)
+DTYPE_NAMES = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.float16: "fp16"}
 
 
 def dtype_code(dt):
     try:
         return _DT[dt]
     except KeyError:
-        raise TypeError("fasterseg_amd kernels support float32 and bfloat16, got %s" % dt)
+        raise TypeError("fasterseg_amd kernels support float32, bfloat16 and (inference only) float16, got %s" % dt)
+
+
+def elem_size(dt):
+    """Bytes per element of a storage type (a torch dtype or an fs_dtype code)."""
+    if not isinstance(dt, torch.dtype):
+        if dt not in _DT.values():
+            raise TypeError("unknown fs_dtype code %r" % (dt,))
+        return 4 if dt == FS_F32 else 2
+    dtype_code(dt)
+    return 4 if dt == torch.float32 else 2
 
 
 def vec_of(dt):
-    return 4 if dt == torch.float32 else 8
+    """Elements per 16-byte vector."""
+    return 16 // elem_size(dt)
+
+
+def require_train_dtype(dt, what):
+    if dt not in TRAIN_DTYPES:
+        raise TypeError("%s: training runs in float32 or bfloat16, got %s (float16 is an inference-engine storage type)" % (what, dt))
 
 
 def round_up(v, m):
@@ -386,7 +405,8 @@ def conv_stem_u8(img_nhwc, w_packed, cout, scale, shift, relu, dtype, mean, std,
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     if out is None:
         out = empty_nhwc(N, cout, Ho, Wo, dtype, img_nhwc.device)
-    call("fs_conv_stem_u8_fwd", _stream(), N, H, W, cout, _p(img_nhwc), _p(w_packed), _p(scale), _p(shift), _p(out),
+    # (float16 goes through the three-type entry point: fs_conv_stem_u8_fwd keeps its published fp32 / bf16 contract)
+    call("fs_conv_stem_u8_infer_fwd" if dtype == torch.float16 else "fs_conv_stem_u8_fwd", _stream(), N, H, W, cout, _p(img_nhwc), _p(w_packed), _p(scale), _p(shift), _p(out),
          channel_stride(out), dtype_code(dtype), int(relu), *([float(v) for v in mean] + [float(v) for v in std]))
     return out
 

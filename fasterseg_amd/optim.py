@@ -26,6 +26,8 @@ class FlatSGD:
         the [O][R][S][I] pack the forward conv reads and the rotated [I][R][S][O] pack of the data-gradient conv - rewritten
         by the update kernel itself, so train-mode convs read (slices of) them in place instead of re-packing a filter on
         every forward and backward (two fs_pack_weight launches per conv per pass: ~10 % of a supernet step's GPU time)."""
+        if pack_dtype is not None:
+            K.require_train_dtype(pack_dtype, "FlatSGD(pack_dtype)")
         self.sync = sync
         self.lr, self.momentum, self.weight_decay, self.max_norm = lr, momentum, weight_decay, max_norm
         # unused: what happens to a parameter that receives no gradient in a step.  "skip" = torch >= 2.0 (zero_grad(set_to_none=True):

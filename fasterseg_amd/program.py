@@ -189,7 +189,7 @@ class _Lowering:
         self.groups = groups                  # BatchNorm groups: the batch is this many independently normalised inputs
         self.dtype = dtype
         self.dt = K.dtype_code(dtype)
-        self.esize = 4 if dtype == torch.float32 else 2
+        self.esize = K.elem_size(dtype)
         self.want_w = want_w                  # network weights receive gradients (through the flat-buffer sink)
         self.sink = sink
         self.touched = []
@@ -636,7 +636,7 @@ def pair_merge_program(x_shape, dtype, need_coef):
     if prog is None:
         n2, C, H, W = x_shape
         assert n2 % 2 == 0
-        esize = 4 if dtype == torch.float32 else 2
+        esize = K.elem_size(dtype)
         dt = K.dtype_code(dtype)
         pixels = (n2 // 2) * H * W
         half = pixels * C * esize

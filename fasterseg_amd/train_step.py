@@ -19,6 +19,10 @@ from .parallel import FlatGradientSync, broadcast_parameters
 class StudentDistillStep:
     def __init__(self, batch, height, width, lr=0.01, momentum=0.9, weight_decay=5e-4, teacher_engine_dtype=None, seed=12345,
                  device="cuda", compute_dtype=torch.float32, fused_loss=None, arch_states=None, class_weight=None):
+        if teacher_engine_dtype == torch.float16:
+            # the fused KL head (fs_kl_distill_up_*) reads the teacher's low-resolution logits in fp32 / bf16 only
+            raise ValueError("StudentDistillStep: teacher_engine_dtype=torch.float16 is not supported: the fused distillation head reads "
+                             "the teacher engine's low-resolution logits in float32 or bfloat16 only")
         self.device = torch.device(device)
         self.compute_dtype = compute_dtype      # activation storage / MFMA operand type; master weights, BN statistics,
         # accumulators and gradients of parameters stay fp32

@@ -15,8 +15,20 @@
  *    already offset to the first channel of the slice and `*_cs` is the number of elements between
  *    consecutive pixels, so an operand can be a channel slice of a wider buffer (torch.cat fused away).
  *    All slices must start on a 16-byte boundary and have C % FS_VEC == 0 unless stated otherwise.
- *  - dtype: FS_F32 (fp32 storage, exact-fp32 MFMA) or FS_BF16 (bf16 storage, fp32 accumulate).
- *    scale/shift/bias/statistics are always fp32.
+ *  - dtype: FS_F32 (fp32 storage, exact-fp32 MFMA), FS_BF16 (bf16 storage, fp32 accumulate) or FS_F16 (IEEE half storage, fp32
+ *    accumulate).  scale/shift/bias/statistics are always fp32.
+ *    FS_F16 is an INFERENCE storage type (an additional value of an existing field: no struct or signature changed, so FS_ABI_VERSION
+ *    stays; a library built before it answers FS_ERR_INVALID "bad dtype" for it).  The entry points an inference engine or an
+ *    evaluator issues take it (fs_pack_weight / fs_pack_weight_frag, fs_refresh_weights with fs_refresh_entry_chunks_infer,
+ *    fs_conv_stem_u8_infer_fwd - the two entry points published with an fp32 / bf16 dtype contract, fs_conv_stem_u8_fwd and
+ *    fs_refresh_entry_chunks, keep it and have these three-type forms beside them -, fs_conv2d_fwd[_ws] without `stats` / FS_CONV_TRANSPOSED / FS_CONV_ACCUM, fs_factorized_reduce_fwd,
+ *    fs_conv3x3_s1_fwd without `stats`, fs_conv3x3_pw_fwd, fs_zoom_cell_fwd, fs_conv_stem_fwd, fs_bilinear_fwd, fs_bilinear_argmax,
+ *    fs_affine_act, fs_copy_channels, the layout conversions, the fs_eval_* accumulators and fs_exec_program's commands for these);
+ *    every training entry point (BatchNorm passes, gradients, weighted sums, loss heads, fs_heads_confusion, the optimizer's packs)
+ *    answers FS_ERR_INVALID / FS_ERR_UNSUPPORTED for it, before any launch.
+ *    fp32 -> fp16 conversion, everywhere a kernel stores FS_F16: round to nearest even; a FINITE value beyond +-65504, including one
+ *    that would round up to infinity (65520 and above), and an infinity are stored as +-65504 (saturation: an infinity would turn into
+ *    NaN at the next bilinear tap of weight 0 and poison an arg-max); NaN stays NaN.
  *  - Every call only enqueues work on `stream` (a hipStream_t passed as void*) and returns; no
  *    allocation, no synchronisation, safe under hipGraph capture.
  *  - Return value: FS_OK or an error code; fs_last_error() gives a thread-local message.  Nothing
@@ -30,7 +42,7 @@ extern "C" {
 #endif
 
 typedef enum { FS_OK = 0, FS_ERR_INVALID = 1, FS_ERR_UNSUPPORTED = 2, FS_ERR_LAUNCH = 3 } fs_status;
-typedef enum { FS_F32 = 0, FS_BF16 = 1 } fs_dtype;
+typedef enum { FS_F32 = 0, FS_BF16 = 1, FS_F16 = 2 } fs_dtype;
 
 /* flags for fs_conv_desc.flags */
 #define FS_CONV_RELU        1   /* y = max(y, 0) after scale/shift            (nn.ReLU, operations.py:74,147) */
@@ -179,7 +191,7 @@ fs_status fs_conv3x3_s1_fwd(void* stream, const fs_conv_desc* d, const void* x, 
 fs_status fs_conv3x3_halo_plan(const fs_conv_desc* d, int has_stats, int* tile, int* ksplit, long long* workgroups);
 
 /* 3x3 / stride 1 / pad 1 LDS-halo convolution and the pointwise (1x1) convolution behind it in ONE launch (conv3x3_pw.hip, ABI 220;
- * inference epilogues, bf16: an fp32 descriptor is FS_ERR_UNSUPPORTED and the caller keeps the separate launches):
+ * inference epilogues, 16-bit storage types (FS_BF16, FS_F16): an fp32 descriptor is FS_ERR_UNSUPPORTED and the caller keeps the separate launches):
  *   x (N,H,W,Cin) -3x3 * scale + shift, ReLU if FS_PW_RELU_3X3-> C3 -1x1 * scale_post + shift_post, ReLU if FS_PW_RELU_POST-> y (N,H,W,Cout)
  * i.e. heads.conv_3x3 -> heads.conv_1x1 (model_seg.py:345; seg_oprs.py:22,245) or an arm's 3x3 whose only reader is a 1x1
  * (model_seg.py:322-334), with the arithmetic of the separate launches: the 3x3's result is rounded to the storage type where the
@@ -210,7 +222,7 @@ fs_status fs_conv3x3_pw_fwd(void* stream, const fs_conv_pw_desc* d, const void* 
  * Replaces BasicResidual_downup_2x.forward (search/operations.py:435-446; F.interpolate :437, conv1/bn1/relu :438-440,
  * conv2/bn2 :441-442, F.interpolate :444, relu :445) and, with down = up = 0, the stride-1 BasicResidual2x.forward
  * (:352-359).  Both filter banks in fragment order (fs_pack_weight_frag).  The intermediate maps never leave the CU: no
- * workspace.  fs_zoom_cell_supported tells whether a geometry is handled (Cmid == Cout <= 256 (bf16) / 128 (fp32), even H, W
+ * workspace.  fs_zoom_cell_supported tells whether a geometry is handled (Cmid == Cout <= 256 (bf16, fp16) / 128 (fp32), even H, W
  * when resampling); callers fall back to the separate launches otherwise. */
 typedef struct fs_zoom_desc {
     int N, H, W, Cin;       /* input map                                                        */
@@ -256,8 +268,13 @@ fs_status fs_conv_stem_fwd(void* stream, int N, int H, int W, int Cout, const fl
 fs_status fs_conv_stem_u8_fwd(void* stream, int N, int H, int W, int Cout, const unsigned char* img, const float* w_packed,
                               const float* scale, const float* shift, void* y, int y_cs, int dtype, int relu,
                               float mean_r, float mean_g, float mean_b, float std_r, float std_g, float std_b);
+/* fs_conv_stem_u8_fwd for the three storage types (FS_F16 too): the same kernels and arguments.  fs_conv_stem_u8_fwd itself keeps the
+ * dtype contract it was published with (fp32 / bf16, anything else "bad dtype"); an fp16 inference engine and FS_OP_STEM_U8 issue this one. */
+fs_status fs_conv_stem_u8_infer_fwd(void* stream, int N, int H, int W, int Cout, const unsigned char* img, const float* w_packed,
+                                    const float* scale, const float* shift, void* y, int y_cs, int dtype, int relu,
+                                    float mean_r, float mean_g, float mean_b, float std_r, float std_g, float std_b);
 
-/* test hook: 0 = fs_conv_stem_fwd always takes the direct vector-ALU kernel, 1 (default) = bf16 outputs take the MFMA form */
+/* test hook: 0 = fs_conv_stem_fwd always takes the direct vector-ALU kernel, 1 (default) = bf16 and fp16 outputs take the MFMA form */
 void fs_debug_stem_mfma(int on);
 /* test hook (ABI 219): 0 (default) = the MFMA stem's grid is min(tiles, 4 blocks per compute unit); n > 0 caps it at n blocks, so that
    every block walks many 4 x 64 tiles of a small image */
@@ -468,7 +485,7 @@ fs_status fs_sgd_momentum_multi(void* stream, const fs_sgd_tensor* tensors, cons
 #define FS_REFRESH_BIAS      3
 typedef struct fs_refresh_entry {
     int kind;               /* FS_REFRESH_*                                                                     */
-    int dtype;              /* packs: fs_dtype of dst                                                           */
+    int dtype;              /* packs: fs_dtype of dst (FS_F16: validate with fs_refresh_entry_chunks_infer)     */
     int Cout, Cin;          /* packs: filter block packed; fold / bias: Cout = channels written (Cin unused)    */
     int R, S;               /* packs: taps (3 x 3 for FS_REFRESH_PACK_FRAG)                                     */
     int lo;                 /* fold: first channel of the BatchNorm module that is read                         */
@@ -486,6 +503,9 @@ int fs_refresh_chunk_elems(void);
  * Host only, no device needed.  -1 with a message in fs_last_error for an entry the kernel must not see: unknown kind, Cout or Cin
  * below 1, taps below 1 or other than 3 x 3 for a fragment pack, a bad dtype, a negative stride or lo, a null source or destination. */
 long long fs_refresh_entry_chunks(const fs_refresh_entry* e);
+/* The same validator with FS_F16 packs allowed (fs_refresh_entry_chunks keeps its published fp32 / bf16 contract): what an fp16
+ * inference engine validates its table with.  The kernel packs the three storage types; chunk counts depend on the element count only. */
+long long fs_refresh_entry_chunks_infer(const fs_refresh_entry* e);
 fs_status fs_refresh_weights(void* stream, const fs_refresh_entry* entries, int n_entries, const int* chunks, int n_chunks);
 
 /* --- OHEM cross-entropy on NCHW fp32 logits ------------------------- */
@@ -567,7 +587,7 @@ typedef struct fs_heads_desc {
     int N, h, w;            /* low-resolution logits of every head: (N, h, w, C) NHWC               */
     int C;                  /* classes, 1..32                                                       */
     int H, W;               /* output = label size                                                  */
-    int dtype;              /* fs_dtype of every head                                               */
+    int dtype;              /* fs_dtype of every head (FS_F32 / FS_BF16)                            */
     int cs[FS_MAX_HEADS];   /* channel stride of head k: a multiple of 4, >= round_up(C, 4); pad lanes readable */
 } fs_heads_desc;
 /* heads: HOST array of K device pointers; gt: (N, H, W) uint8 / int32 / int64 (gt_bytes 1 / 4 / 8); hist (K * C * C) and counts
@@ -618,7 +638,7 @@ typedef struct fs_logits_desc {
     int N, h, w;            /* low-resolution logits (N, h, w, C), NHWC                              */
     int C, cs;              /* classes (<= 20) and channel stride (multiple of 4, C <= cs <= 64)     */
     int H, W;               /* resolution of the labels = of the virtual up-sampled logits           */
-    int dtype;              /* fs_dtype of the logits (and of their gradient)                        */
+    int dtype;              /* fs_dtype of the logits (and of their gradient); FS_F16: fs_eval_* only */
 } fs_logits_desc;
 fs_status fs_ohem_ce_up_fwd(void* stream, const fs_logits_desc* d, const void* logits_lo, const long long* target, int ignore,
                             float* true_prob, float* nll, float* lse);
