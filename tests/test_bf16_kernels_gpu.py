@@ -1,26 +1,28 @@
-"""FS_F16 through the inference kernels on a real MI355X.
+"""FS_BF16 through the inference kernels on a real MI355X, held to the bars of tests/test_f16_kernels_gpu.py: the same entry points,
+geometries, flags and debug hooks, with bfloat16 storage.  Helpers and bound formulas: tests/_bounds.py, unit roundoff E = 2^-8.
 
-1. The conversion rule of include/fasterseg_hip.h on a fixed table (ties, 65504, 65519, 65520, 1e6, their negatives, +-0, NaN): the bits
-   of np.clip(x, -65504, 65504).astype(np.float16); fp16 -> fp32 is exact.
-2. Exact contractions.  x in {j / 512, |j| <= 512} needs 10 bits (exact in fp16, NOT in bf16), w in {j / 8, |j| <= 8}; with
-   K = 9 * Cin <= 576 every partial sum is a multiple of 2^-12 below 2^10 - 22 bits, exact in fp32 in any order - so the output must be
-   round-to-nearest-even of the exact sum, bit for bit.  A kernel that contracted in bf16, dropped a tap or a channel, or rounded twice
-   cannot give those bits.  Two-stage kernels (fs_conv3x3_pw_fwd, fs_zoom_cell_fwd) round the first stage to fp16 where the separate
-   launches store it; their second filter is in {-1, 0, 1} and sparse so that the second contraction is exactly summable too (asserted
-   on the CPU for the operands used: every sum of |terms| is a multiple of 2^-12 below 2^12).  The zoom cell is exact with its 1/2
-   down-sample from 4 x 4 (taps land on pixels: scale 3) and without the x2 up-sample, whose weights (multiples of 1/3 ...) are not exact;
+1. Conversion on a fixed table of normal fp32 values: fs_nchw_to_nhwc into bf16 gives the bits of torch's fp32 -> bf16 conversion (round to
+   nearest even; ties both ways around 1 + k 2^-8; a value at or beyond the midpoint above the largest finite bf16 becomes infinity -
+   bf16 does not saturate, unlike fp16; +-0 keep their sign; NaN stays NaN and nothing else becomes one); bf16 -> fp32 is exact.  fp32
+   subnormals are left out: what the hardware converter does with them is not measured.
+2. Exact contractions.  x in {j / 256, |j| <= 256} needs all 8 significand bits (asserted), w in {j / 8, |j| <= 8}; with
+   K = 9 * Cin <= 576 every partial sum is a multiple of 2^-11 below 2^10 - 21 bits, exact in fp32 in any order - so the output must be
+   round-to-nearest-even of the exact sum, bit for bit.  A kernel that truncated the store, lost an operand bit, dropped a tap or a
+   channel, or rounded twice cannot give those bits.  Two-stage kernels (fs_conv3x3_pw_fwd, fs_zoom_cell_fwd) round the first stage to
+   bf16 where the separate launches store it; their second filter is in {-1, 0, 1} and sparse so that the second contraction is exactly
+   summable too (asserted on the CPU for the operands used: every sum of |terms| is a multiple of 2^-12 below 2^12).  The zoom cell is
+   exact with its 1/2 down-sample from 4 x 4 (taps land on pixels: scale 3) and without the x2 up-sample, whose weights are not exact;
    the up-sample is covered by the random cells.
-3. Random operands, rounded to fp16 first, against an fp64 reference on the rounded operands, over the case tables of the existing bf16
-   tests.  Single-stage kernels, per element:
-       |got - ref| <= 2^-11 |ref| + K 2^-23 sum|x w| + 2^-24
+3. Random operands, rounded to bf16 first, against an fp64 reference on the rounded operands, over the case tables of the fp16 file.
+   Single-stage kernels, per element:
+       |got - ref| <= 2^-8 |ref| + K 2^-23 sum|x w| + 2^-24
    (one output rounding + the fp32 accumulation bound; K = taps x channels, 4 for a resample).  Kernels that round an intermediate map
-   to fp16 (a resample folded into the conv staging, the 3x3 -> 1x1 pair, the zoom cell) get the same bound PROPAGATED stage by stage:
-   an input known to e gives the contraction sum|w| e more, scale / shift add two fp32 roundings, and each stored stage adds
-   2^-11 (|value| + its error) + 2^-24 (`_stage` below).  The stems: the existing fp32 bound 1e-4 + 1e-4 |ref| plus 2^-11 |ref|.
+   to bf16 (a resample folded into the conv staging, the 3x3 -> 1x1 pair, the zoom cell) get the same bound PROPAGATED stage by stage
+   (tests/_bounds.py `_stage`, `_resample`).  The stems: the existing fp32 bound 1e-4 + 1e-4 |ref| plus 2^-8 |ref|.
 4. fs_bilinear_argmax equals the arg-max of the fp64 up-sample wherever the top-two margin exceeds twice the resample bound, takes the
-   lowest index on exact ties, and at most 1 % of the pixels are excluded by the margin rule (seed checked on the CPU).
-5. fs_refresh_weights into fp16 writes the bytes of fs_pack_weight / fs_pack_weight_frag.
-6. fs_eval_score_accumulate on fp16 logits against the fp64 up-sample (canvas and class map, with and without the flipped image).
+   lowest index on exact ties, and at most 1 % of the pixels are excluded by the margin rule (asserted before the launch).
+5. fs_refresh_weights into bf16 writes the bytes of fs_pack_weight / fs_pack_weight_frag.
+6. fs_eval_score_accumulate on bf16 logits against the fp64 up-sample (canvas and class map, with and without the flipped image).
 
 Where this is looser than a literal reading of the single formula: the multi-stage kernels use the propagated bound above; the arg-max
 margin is twice the resample bound (both candidates carry it); the zoom table is cut to maps of at most 8192 pixels and the stem table
@@ -43,9 +45,9 @@ from tests import test_logits_upsample_tiled_gpu as LT
 from tests import test_zoom_cell_gpu as ZC
 
 pytestmark = pytest.mark.gpu
-H16 = torch.float16
-_B = B.For(H16)
-E16, E32, TINY = B.UNIT[H16], B.E32, B.TINY
+BF = torch.bfloat16
+_B = B.For(BF)
+EBF, E32, TINY = B.UNIT[BF], B.E32, B.TINY
 grid, bits, conv64, assert_within, _second_stage_exact = B.grid, B.bits, B.conv64, B.assert_within, B._second_stage_exact
 rnd16, rne16, dev16, single_bound, _stage, _resample, _argmax_inputs = (_B.rnd16, _B.rne16, _B.dev16, _B.single_bound, _B._stage, _B._resample,
                                                                          _B._argmax_inputs)
@@ -57,32 +59,51 @@ def K():
 
 
 # ---- 1. conversion -------------------------------------------------------------------------------------------------------------------
+BF_MAX = (2.0 - 2.0 ** -7) * 2.0 ** 127                 # 0x7f7f, the largest finite bf16
+BF_MID = (2.0 - 2.0 ** -8) * 2.0 ** 127                 # half-way to 2^128: the tie goes to the even neighbour, infinity
+F32_MAX = (2.0 - 2.0 ** -23) * 2.0 ** 127
+
+
+def conversion_table():
+    u = 2.0 ** -8                                         # half a bf16 ulp at 1
+    base = [1.0 + u, 1.0 + 3 * u, 1.0 + 2 * u, 1.0 + u + 2.0 ** -23, BF_MAX, BF_MID - 2.0 ** 104, BF_MID, F32_MAX, 0.0, 0.333251953125,
+            1000.5, 2.0 ** -100]
+    table = np.array(base + [-v for v in base] + [float("nan"), float("inf"), -float("inf"), 0.1, -0.1, 3.39e38, 1.0 + 3 * u - 2.0 ** -23, 65520.0])
+    table = table.astype(np.float32)
+    assert table.size == 32 and (np.abs(table[np.isfinite(table) & (table != 0)]) >= 2.0 ** -126).all(), "no fp32 subnormals"
+    return table
+
+
 def test_conversion_table_round_trip():
     k = K()
-    u = 2.0 ** -11
-    base = [1.0 + u, 1.0 + 3 * u, 1.0 + 2 * u, 65504.0, 65519.0, 65520.0, 1e6, 0.0, 0.333251953125, 1000.5, 2.0 ** -14, 3.0e38]
-    table = np.array(base + [-v for v in base] + [float("nan"), 65519.99, 65535.0, 70000.0, float("inf"), -float("inf"), 0.1, -0.1],
-                     dtype=np.float32)
-    assert table.size == 32
+    table = conversion_table()
     x = torch.from_numpy(table).view(1, 8, 2, 2).clone()                     # (N, C, H, W): every value is one (pixel, channel)
-    y = k.to_nhwc(x.cuda(), H16)
-    want = np.clip(table, -65504.0, 65504.0).astype(np.float16).reshape(1, 8, 2, 2)
-    got = bits(y).numpy().view(np.float16)
-    nan = np.isnan(table).reshape(1, 8, 2, 2)
-    assert np.array_equal(np.isnan(got), nan), "NaN must stay NaN and nothing else may become one"
-    assert np.array_equal(got.view(np.int16)[~nan], want.view(np.int16)[~nan]), (got[~nan], want[~nan])
-    assert not np.isinf(got).any(), "a finite value or an infinity was stored as infinity instead of +-65504"
-    assert got.view(np.uint16).reshape(-1)[7] == 0x0000 and got.view(np.uint16).reshape(-1)[19] == 0x8000      # +0, -0 keep their sign
-    back = k.to_nchw(y).cpu().numpy()
-    assert np.array_equal(back[~nan], got.astype(np.float32)[~nan]) and np.isnan(back[nan]).all(), "fp16 -> fp32 must be exact"
+    want = bits(x.to(BF))                                                     # torch's conversion on the CPU: round to nearest even
+    wf = x.to(BF).float().view(-1)
+    assert float(wf[0]) == 1.0 and float(wf[1]) == 1.0 + 2.0 ** -6 and float(wf[3]) == 1.0 + 2.0 ** -7, "the ties go to even, both ways"
+    assert float(wf[4]) == BF_MAX and float(wf[5]) == BF_MAX and float(wf[29]) == BF_MAX
+    assert bool(torch.isinf(wf[[6, 7, 18, 19, 25, 26]]).all()), "bf16 does not saturate: the midpoint and beyond round to infinity"
+    y = k.to_nhwc(x.cuda(), BF)
+    got = bits(y)
+    nan = torch.isnan(x)
+    gotf = got.view(BF).float()
+    assert torch.equal(torch.isnan(gotf), nan), "NaN must stay NaN and nothing else may become one"
+    assert torch.equal(got[~nan], want[~nan]), (gotf[~nan], want.view(BF).float()[~nan])
+    flat = got.view(-1).numpy().view(np.uint16)
+    assert flat[8] == 0x0000 and flat[20] == 0x8000                           # +0, -0 keep their sign
+    back = k.to_nchw(y).cpu()
+    assert torch.equal(back[~nan], gotf[~nan]) and bool(torch.isnan(back[nan]).all()), "bf16 -> fp32 must be exact"
 
 
 # ---- 2. exact contractions -------------------------------------------------------------------------------------------------------------
 def _exact_ops(N, cin, H, W, cout, ksize, seed):
-    x = grid(N, cin, H, W, seed=seed, den=512, lim=512)
+    x = grid(N, cin, H, W, seed=seed, den=256, lim=256)
     w = grid(cout, cin, ksize, ksize, seed=seed + 1, den=8, lim=8)
     assert ksize * ksize * cin <= 576
-    assert float(x.to(torch.bfloat16).double().sub(x).abs().max()) > 0, "the operands must not be representable in bf16"
+    xb = x.float().to(BF)
+    assert bool((xb.double() == x).all()) and bool((w.float().to(BF).double() == w).all()), "the operands must be bf16 numbers"
+    cleared = (xb.view(torch.int16) & ~1).view(BF)
+    assert bool((cleared != xb).any()), "some x must need all 8 significand bits"
     return x, w
 
 
@@ -92,7 +113,7 @@ def test_exact_conv2d(case):
     N, cin, H, W, cout, ks, stride, pad = case
     x, w = _exact_ops(N, cin, H, W, cout, ks, seed=11)
     want = rne16(conv64(x, w, stride, pad))
-    y = k.conv2d(dev16(x), k.pack_weight(w.float().cuda(), H16), cout, ks, ks, stride, pad)
+    y = k.conv2d(dev16(x), k.pack_weight(w.float().cuda(), BF), cout, ks, ks, stride, pad)
     assert torch.equal(bits(y), bits(want)), float((y.double().cpu() - want.double()).abs().max())
 
 
@@ -106,9 +127,9 @@ def test_exact_conv3x3_s1(form):
         ks_flag = {"ksplit": True, "ksplit16": 16, "no_ksplit": False, "unaligned_slice": None}[form]
     x, w = _exact_ops(N, cin, H, W, cout, 3, seed=21)
     want = rne16(conv64(x, w, 1, 1))
-    xd, wf = dev16(x), k.pack_weight_frag(w.float().cuda(), H16)
+    xd, wf = dev16(x), k.pack_weight_frag(w.float().cuda(), BF)
     if form == "unaligned_slice":
-        wide = k.empty_nhwc(N, cout + 8, H, W, H16, "cuda", zero=True)
+        wide = k.empty_nhwc(N, cout + 8, H, W, BF, "cuda", zero=True)
         out = wide[:, 4:4 + cout]
         assert out.data_ptr() % 16 == 8
         k.conv3x3_halo(xd, wf, cout, out=out)
@@ -121,7 +142,7 @@ def test_exact_conv3x3_s1(form):
 
 @pytest.mark.parametrize("rows", [4, 8], ids=["rows4", "rows8"])
 def test_exact_conv3x3_pw(rows):
-    """Cin 32, C3 64, Cout 19 in a 20-channel pixel stride: the 3x3 (ReLU) rounded to fp16 as the separate launch stores it, then the 1x1"""
+    """Cin 32, C3 64, Cout 19 in a 20-channel pixel stride: the 3x3 (ReLU) rounded to bf16 as the separate launch stores it, then the 1x1"""
     k = K()
     N, cin, H, W, c3, cout = 1, 32, 9, 33, 64, 19
     x, w3 = _exact_ops(N, cin, H, W, c3, 3, seed=31)
@@ -129,10 +150,10 @@ def test_exact_conv3x3_pw(rows):
     t = rne16(F.relu(conv64(x, w3, 1, 1))).double()
     _second_stage_exact(t, w2, 0)
     want = rne16(conv64(t, w2, 1, 0))
-    buf = torch.full((N, H, W, 20), 7.0, dtype=H16, device="cuda")
+    buf = torch.full((N, H, W, 20), 7.0, dtype=BF, device="cuda")
     out = buf.permute(0, 3, 1, 2)[:, :cout]
     assert k.channel_stride(out) == 20
-    k.conv3x3_pw(dev16(x), k.pack_weight_frag(w3.float().cuda(), H16), c3, None, None, True, k.pack_weight(w2.float().cuda(), H16), cout,
+    k.conv3x3_pw(dev16(x), k.pack_weight_frag(w3.float().cuda(), BF), c3, None, None, True, k.pack_weight(w2.float().cuda(), BF), cout,
                  None, None, False, out=out, rows=rows)
     assert torch.equal(bits(out), bits(want)), float((out.double().cpu() - want.double()).abs().max())
     assert bool((buf[..., cout:] == 7.0).all()), "the pad channel of the 20-channel stride was written"
@@ -152,7 +173,7 @@ def test_exact_zoom_cell(down):
     t = rne16(F.relu(conv64(v, w1, 1, 1))).double()
     _second_stage_exact(t, w2, 1)
     want = rne16(F.relu(conv64(t, w2, 1, 1)))
-    y = k.zoom_cell(dev16(x), k.pack_weight_frag(w1.float().cuda(), H16), None, None, k.pack_weight_frag(w2.float().cuda(), H16), None, None,
+    y = k.zoom_cell(dev16(x), k.pack_weight_frag(w1.float().cuda(), BF), None, None, k.pack_weight_frag(w2.float().cuda(), BF), None, None,
                     C, C, down=bool(down), up=False)
     assert torch.equal(bits(y), bits(want)), float((y.double().cpu() - want.double()).abs().max())
 
@@ -173,8 +194,8 @@ def test_random_conv2d(geom, cfg):
     try:
         _lib.lib().fs_debug_force_conv_cfg(cfg)
         ohw = G.out_hw(H, W, ks, stride, pad)                                 # (pad -1: FactorizedReduce's x[:, :, 1:, 1:] branch)
-        y = k.conv2d(dev16(x), k.pack_weight(w.float().cuda(), H16), cout, ks, ks, stride, pad, out_hw=ohw)
-        yr = k.conv2d(dev16(x), k.pack_weight(w.float().cuda(), H16), cout, ks, ks, stride, pad, relu=True, out_hw=ohw)
+        y = k.conv2d(dev16(x), k.pack_weight(w.float().cuda(), BF), cout, ks, ks, stride, pad, out_hw=ohw)
+        yr = k.conv2d(dev16(x), k.pack_weight(w.float().cuda(), BF), cout, ks, ks, stride, pad, relu=True, out_hw=ohw)
     finally:
         _lib.lib().fs_debug_force_conv_cfg(-1)
     assert_within(y, ref, single_bound(ref, mag, ks * ks * cin), "fs_conv2d_fwd")
@@ -189,18 +210,14 @@ def test_random_factorized_reduce():
     x = rnd16(N, cin, H, W, seed=140)
     ws = [rnd16(half, cin, 1, 1, seed=141 + j, scale=(2.0 / cin) ** 0.5) for j in range(2)]
     xd = dev16(x)
-    out = k.empty_nhwc(N, 2 * half, H // 2, W // 2, H16, "cuda", zero=True)
-    wp = [k.pack_weight(w.float().cuda(), H16) for w in ws]
-    ds = [k.conv_desc(x.shape, k.channel_stride(xd), half, 1, 1, 2, -j, 2 * half, H16, out_hw=(H // 2, W // 2)) for j in range(2)]
+    out = k.empty_nhwc(N, 2 * half, H // 2, W // 2, BF, "cuda", zero=True)
+    wp = [k.pack_weight(w.float().cuda(), BF) for w in ws]
+    ds = [k.conv_desc(x.shape, k.channel_stride(xd), half, 1, 1, 2, -j, 2 * half, BF, out_hw=(H // 2, W // 2)) for j in range(2)]
     _lib.call("fs_factorized_reduce_fwd", k._stream(), ctypes.byref(ds[0]), k._p(xd), k._p(wp[0]), k._p(out[:, :half]), None,
               ctypes.byref(ds[1]), k._p(xd), k._p(wp[1]), k._p(out[:, half:]), None)
     for j in range(2):
         ref, mag = conv64(x, ws[j], 2, -j), conv64(x.abs(), ws[j].abs(), 2, -j)
         assert_within(out[:, j * half:(j + 1) * half], ref, single_bound(ref, mag, cin), "fs_factorized_reduce_fwd branch %d" % j)
-    stats = torch.zeros(2 * half, device="cuda")
-    status = _lib.lib().fs_factorized_reduce_fwd(k._stream(), ctypes.byref(ds[0]), k._p(xd), k._p(wp[0]), k._p(out[:, :half]), k._p(stats),
-                                                 ctypes.byref(ds[1]), k._p(xd), k._p(wp[1]), k._p(out[:, half:]), None)
-    assert status == 2, "BatchNorm statistics are training: refused for FS_F16"
 
 
 HALO_CASES = ([(1, c * 32, 16, 32, 64, f) for c in (1, 2, 3, 4, 6, 8) for f in HK.FORMS if c > 1 or f is True] +      # test_ksplit_chunk_counts
@@ -216,7 +233,7 @@ def test_random_conv3x3_s1(case):
     x = rnd16(N, cin, H, W, seed=200 + cin)
     w = rnd16(cout, cin, 3, 3, seed=201 + cin, scale=(2.0 / (cin * 9)) ** 0.5)
     ref, mag = conv64(x, w, 1, 1), conv64(x.abs(), w.abs(), 1, 1)
-    xd, wf = dev16(x), k.pack_weight_frag(w.float().cuda(), H16)
+    xd, wf = dev16(x), k.pack_weight_frag(w.float().cuda(), BF)
     y = k.conv3x3_halo(xd, wf, cout, ksplit=form)
     assert_within(y, ref, single_bound(ref, mag, 9 * cin), "fs_conv3x3_s1_fwd")
     if form is False:                                                          # the forced output-channel tiles of the plain form, and stride 2
@@ -229,7 +246,7 @@ def test_random_conv3x3_s1(case):
 @pytest.mark.parametrize("ksplit", [True, 16, False], ids=["ks32", "ks16", "plain"])
 @pytest.mark.parametrize("case", HK.VRES_CASES, ids=["%dx%dc-%dx%d-to-%dx%d-%d" % c for c in HK.VRES_CASES])
 def test_random_resample_at_staging(case, ksplit):
-    """conv(relu(resample(x))) in one launch: the staged sample is rounded to fp16 (first stage of the chain), then the convolution"""
+    """conv(relu(resample(x))) in one launch: the staged sample is rounded to bf16 (first stage of the chain), then the convolution"""
     k = K()
     N, chunks, Hs, Ws, H, W, cout = case
     cin = chunks * 32
@@ -237,10 +254,10 @@ def test_random_resample_at_staging(case, ksplit):
     w = rnd16(cout, cin, 3, 3, seed=301 + cin, scale=(2.0 / (cin * 9)) ** 0.5)
     v, e = _resample(x, None, (H, W), relu=True)
     ref, bound = _stage(v, e, w, None, None, True)
-    xd, wf = dev16(x), k.pack_weight_frag(w.float().cuda(), H16)
+    xd, wf = dev16(x), k.pack_weight_frag(w.float().cuda(), BF)
     assert_within(k.conv3x3_halo(xd, wf, cout, relu=True, ksplit=ksplit, vres=(H, W, True)), ref, bound, "resample-at-staging")
     if ksplit is False:                                                        # the implicit-GEMM kernel's virtual resize (fs_conv2d_fwd vr_*)
-        assert_within(k.conv2d(xd, k.pack_weight(w.float().cuda(), H16), cout, 3, 3, 1, 1, relu=True, vres=(H, W, True)), ref, bound,
+        assert_within(k.conv2d(xd, k.pack_weight(w.float().cuda(), BF), cout, 3, 3, 1, 1, relu=True, vres=(H, W, True)), ref, bound,
                       "fs_conv2d_fwd virtual resize")
 
 
@@ -258,9 +275,9 @@ def test_random_conv3x3_pw(ch, rows):
         s2, b2 = (torch.rand(cout, generator=g) + 0.5).double(), (torch.randn(cout, generator=g) * 0.5).double()
         t, e = _stage(x, None, w3, s3, b3, True)
         ref, bound = _stage(t, e, w2, s2, b2, False, pad=0)
-        out = k.empty_nhwc(N, cout, H, W, H16, "cuda", cs=k.round_up(cout, 32 if cout % 8 else 8))
-        k.conv3x3_pw(dev16(x), k.pack_weight_frag(w3.float().cuda(), H16), c3, s3.float().cuda(), b3.float().cuda(), True,
-                     k.pack_weight(w2.float().cuda(), H16), cout, s2.float().cuda(), b2.float().cuda(), False, out=out, rows=rows)
+        out = k.empty_nhwc(N, cout, H, W, BF, "cuda", cs=k.round_up(cout, 32 if cout % 8 else 8))
+        k.conv3x3_pw(dev16(x), k.pack_weight_frag(w3.float().cuda(), BF), c3, s3.float().cuda(), b3.float().cuda(), True,
+                     k.pack_weight(w2.float().cuda(), BF), cout, s2.float().cuda(), b2.float().cuda(), False, out=out, rows=rows)
         assert_within(out, ref, bound, "fs_conv3x3_pw_fwd %s on %dx%dx%d" % (ch, N, H, W))
 
 
@@ -284,7 +301,7 @@ def test_random_zoom_cell(case):
     else:
         ref, bound = _stage(v, e, w2, s2, b2, True)
     sc = [t.float().cuda() for t in (s1, b1, s2, b2)]
-    y = k.zoom_cell(dev16(x), k.pack_weight_frag(w1.float().cuda(), H16), sc[0], sc[1], k.pack_weight_frag(w2.float().cuda(), H16), sc[2], sc[3],
+    y = k.zoom_cell(dev16(x), k.pack_weight_frag(w1.float().cuda(), BF), sc[0], sc[1], k.pack_weight_frag(w2.float().cuda(), BF), sc[2], sc[3],
                     C, C, down=bool(down), up=bool(up))
     assert_within(y, ref, bound, "fs_zoom_cell_fwd")
 
@@ -302,11 +319,11 @@ def test_random_stem(case, mfma):
     ref = F.relu(F.conv2d(x.double(), w.double(), None, 2, 1) * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1))
     try:
         _lib.lib().fs_debug_stem_mfma(mfma)
-        y = k.conv_stem(x.cuda(), k.pack_weight(w.cuda(), torch.float32), cout, scale.cuda(), shift.cuda(), True, H16)
+        y = k.conv_stem(x.cuda(), k.pack_weight(w.cuda(), torch.float32), cout, scale.cuda(), shift.cuda(), True, BF)
     finally:
         _lib.lib().fs_debug_stem_mfma(1)
-    assert y.dtype == H16
-    assert_within(y, ref, 1e-4 + 1e-4 * ref.abs() + E16 * ref.abs(), "fs_conv_stem_fwd")
+    assert y.dtype == BF
+    assert_within(y, ref, 1e-4 + 1e-4 * ref.abs() + EBF * ref.abs(), "fs_conv_stem_fwd")
 
 
 @pytest.mark.parametrize("geom", [(2, 34, 52, 32), (1, 26, 264, 64), (1, 17, 136, 24), (1, 33, 50, 32)], ids=lambda g: "%dx%dx%d-c%d" % g)
@@ -317,9 +334,9 @@ def test_random_stem_u8(geom):
     x = torch.from_numpy(U8.expected(img))
     _, w, scale, shift = S.inputs(cout, (n, h, w_))
     ref = F.relu(F.conv2d(x.double(), w.double(), None, 2, 1) * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1))
-    y = k.conv_stem_u8(torch.from_numpy(img).cuda(), k.pack_weight(w.cuda(), torch.float32), cout, scale.cuda(), shift.cuda(), True, H16,
+    y = k.conv_stem_u8(torch.from_numpy(img).cuda(), k.pack_weight(w.cuda(), torch.float32), cout, scale.cuda(), shift.cuda(), True, BF,
                        U8.MEAN, U8.STD)
-    assert_within(y, ref, 1e-4 + 1e-4 * ref.abs() + E16 * ref.abs(), "fs_conv_stem_u8_fwd")
+    assert_within(y, ref, 1e-4 + 1e-4 * ref.abs() + EBF * ref.abs(), "fs_conv_stem_u8_fwd")
 
 
 @pytest.mark.parametrize("spec", G.RESIZE_TABLE, ids=lambda s: "%dx%dx%dx%d_to_%dx%d_r%d" % (s[0] + s[1] + (s[2],)))
@@ -328,24 +345,24 @@ def test_random_bilinear_nhwc(spec):
     (N, C, Hi, Wi), size, relu = spec
     x = rnd16(N, C, Hi, Wi, seed=600 + C)
     ref, bound = _resample(x, None, size, relu=bool(relu))
-    wide = k.empty_nhwc(N, C + 16, Hi, Wi, H16, "cuda", zero=True)            # a channel slice of a wider buffer, as in the grouped table
+    wide = k.empty_nhwc(N, C + 16, Hi, Wi, BF, "cuda", zero=True)            # a channel slice of a wider buffer, as in the grouped table
     wide[:, 8:8 + C] = dev16(x)
     assert_within(k.bilinear(wide[:, 8:8 + C], size, relu=bool(relu)), ref, bound, "fs_bilinear_fwd NHWC")
 
 
-@pytest.mark.parametrize("mode", [1, 2], ids=["f32out", "f16out"])
+@pytest.mark.parametrize("mode", [1, 2], ids=["f32out", "bf16out"])
 @pytest.mark.parametrize("case", LT.CASES, ids=lambda c: "%dx%dx%d_%dx%d_to_%dx%d" % (c[0], c[1], c[2], c[3][0], c[3][1], c[4][0], c[4][1]))
 def test_random_logits_upsample_nchw(case, mode):
     """tiled form, gather kernel and scalar kernel of the NCHW logits writer (the case table says which shape takes which)"""
     from fasterseg_amd import _lib
     n, c, cs, (hi, wi), size, _ = case
-    x, buf = LT._input(case, H16)
+    x, buf = LT._input(case, BF)
     ref, bound = _resample(torch.from_numpy(x).double(), None, size, store=(mode == 2), exact_taps=True)
     try:
         for tiled in (1, 0):
             _lib.lib().fs_debug_logits_tiled(tiled)
             out = LT._run(buf, case, mode)
-            assert out.dtype == (torch.float32 if mode == 1 else H16)
+            assert out.dtype == (torch.float32 if mode == 1 else BF)
             assert_within(out, ref, bound + (TINY * ref.abs() if mode == 1 else 0.0), "fs_bilinear_fwd NCHW (tiled hook %d)" % tiled)
     finally:
         _lib.lib().fs_debug_logits_tiled(1)
@@ -366,7 +383,7 @@ def test_bilinear_argmax(case):
     assert float(use.double().mean()) >= 0.99
     view = buf.cuda().permute(0, 3, 1, 2)[:, :c]
     classes = torch.full((n,) + tuple(size), 255, dtype=torch.uint8, device="cuda")
-    d = _lib.ResizeDesc(n, hi, wi, size[0], size[1], c, cs, 0, k.dtype_code(H16), 0, 0)
+    d = _lib.ResizeDesc(n, hi, wi, size[0], size[1], c, cs, 0, k.dtype_code(BF), 0, 0)
     _lib.call("fs_bilinear_argmax", k._stream(), ctypes.byref(d), k._p(view), k._p(classes))
     got = classes.cpu().long()
     assert bool((got[use] == want[use]).all()), "%d of %d decided pixels differ" % (int((got[use] != want[use]).sum()), int(use.sum()))
@@ -384,13 +401,13 @@ def test_affine_act_and_copy_channels():
     ref = F.relu(x * s.view(1, -1, 1, 1) + b.view(1, -1, 1, 1))
     mag = (x * s.view(1, -1, 1, 1)).abs() + b.abs().view(1, -1, 1, 1)
     assert_within(k.affine_act(xd, s.float().cuda(), b.float().cuda(), True), ref, single_bound(ref, mag, 2), "fs_affine_act")
-    wide = k.empty_nhwc(N, C + 16, H, W, H16, "cuda", zero=True)
+    wide = k.empty_nhwc(N, C + 16, H, W, BF, "cuda", zero=True)
     k.copy_channels(xd, wide[:, 8:8 + C])
     assert torch.equal(bits(wide[:, 8:8 + C]), bits(xd)) and float(wide[:, :8].abs().max()) == 0.0 and float(wide[:, 8 + C:].abs().max()) == 0.0
 
 
 def test_eval_score_accumulate_against_fp64():
-    """fs_eval_score_accumulate on fp16 logits: exp(l0 (+ l1 mirrored)) of the x8 up-sampled logits added into the fp32 canvas, and the
+    """fs_eval_score_accumulate on bf16 logits: exp(l0 (+ l1 mirrored)) of the x8 up-sampled logits added into the fp32 canvas, and the
     class map of the same sum.  Reference: the fp64 up-sample of tests/_resize_ref.py.  The up-sample's absolute error e (four taps, per
     image) goes through exp as a relative error; exp itself and the canvas addition keep the bar of the existing fp32 / bf16 test
     (tests/test_ms_eval_gpu.py: rtol 1e-5, atol 1e-6): |got - ref| <= ref (2 e + 1e-5) + 1e-6."""
@@ -398,8 +415,8 @@ def test_eval_score_accumulate_against_fp64():
     N, C, h, w, cs = 2, 19, 8, 12, 20
     H, W = 8 * h, 8 * w
     g = torch.Generator().manual_seed(901)
-    x = (torch.randn(N, C, h, w, generator=g) * 2.0).to(H16)
-    buf = torch.randn(N, h, w, cs, generator=g).to(H16)                                  # the pad channel holds junk
+    x = (torch.randn(N, C, h, w, generator=g) * 2.0).to(BF)
+    buf = torch.randn(N, h, w, cs, generator=g).to(BF)                                  # the pad channel holds junk
     buf[..., :C] = x.permute(0, 2, 3, 1)
     logits = buf.cuda().permute(0, 3, 1, 2)[:, :C]
     up, err = _resample(x.double(), None, (H, W), store=False)
@@ -432,14 +449,13 @@ def test_refresh_weights_writes_the_pack_bytes():
     g = torch.Generator().manual_seed(800)
     specs = [(L.FS_REFRESH_PACK, 40, 24, 3), (L.FS_REFRESH_PACK, 19, 128, 1), (L.FS_REFRESH_PACK_FRAG, 40, 24, 3), (L.FS_REFRESH_PACK_FRAG, 72, 200, 3)]
     ws = [(torch.randn(co, ci, ks, ks, generator=g) * 300.0).cuda() for _, co, ci, ks in specs]
-    ws[0][0, 0, 0, 0], ws[0][0, 0, 0, 1], ws[2][0, 0, 0, 0] = 1e6, -70000.0, 65520.0          # saturation happens in the refresh as in the pack
-    want = [k.pack_weight(w, H16) if kind == L.FS_REFRESH_PACK else k.pack_weight_frag(w, H16) for (kind, *_), w in zip(specs, ws)]
+    want = [k.pack_weight(w, BF) if kind == L.FS_REFRESH_PACK else k.pack_weight_frag(w, BF) for (kind, *_), w in zip(specs, ws)]
     got = [torch.full_like(t, 3.0) for t in want]
     entries = (L.RefreshEntry * len(specs))()
     chunks = []
     for i, ((kind, co, ci, ks), w) in enumerate(zip(specs, ws)):
         e = entries[i]
-        e.kind, e.dtype, e.Cout, e.Cin, e.R, e.S = kind, L.FS_F16, co, ci, ks, ks
+        e.kind, e.dtype, e.Cout, e.Cin, e.R, e.S = kind, L.FS_BF16, co, ci, ks, ks
         e.o_stride, e.i_stride = w.stride(0), w.stride(1)
         e.src, e.dst = w.data_ptr(), got[i].data_ptr()
         n = h.fs_refresh_entry_chunks_infer(ctypes.byref(e))
@@ -451,4 +467,3 @@ def test_refresh_weights_writes_the_pack_bytes():
     torch.cuda.synchronize()
     for i, (a, b) in enumerate(zip(got, want)):
         assert torch.equal(a.view(torch.int16), b.view(torch.int16)), specs[i]
-    assert not bool(torch.isinf(got[0].float()).any()) and float(got[0].float().max()) == 65504.0
