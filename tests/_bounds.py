@@ -1,6 +1,7 @@
-"""Per-element error bounds of the 16-bit inference kernels against fp64 references, shared by tests/test_f16_kernels_gpu.py,
-tests/test_bf16_kernels_gpu.py and tests/test_bounds_selfcheck.py.  Every helper takes the storage dtype; `For(dtype)` binds it, so a
-test module names its type once.
+"""Per-element error bounds of the kernels against fp64 references: the 16-bit inference kernels (tests/test_f16_kernels_gpu.py,
+tests/test_bf16_kernels_gpu.py, tests/test_bounds_selfcheck.py) and, in the second half of the module, the training backward kernels
+(tests/test_bwd_bounds_gpu.py, tests/test_bwd_bounds_selfcheck.py, the weight gradients of tests/_grouped_cases.py).  Every helper takes
+the storage dtype; `For(dtype)` binds it, so a test module names its type once.
 
 UNIT[dtype] is the unit roundoff of one round-to-nearest store: half an ulp relative to the value, 2^-p for a p-bit significand (hidden
 bit included).  fp16 has 11 bits, bf16 has 8: 2^-8, not 2^-9 - a correctly rounded bf16 value just above a power of two is off by up to
@@ -8,14 +9,18 @@ bit included).  fp16 has 11 bits, bf16 has 8: 2^-8, not 2^-9 - a correctly round
     |got - ref| <= UNIT |ref| + K 2^-23 sum|x w| + 2^-24
 (one output rounding + the fp32 accumulation bound; K = taps x channels, 4 for a resample).  Kernels that round an intermediate map to
 the storage type get the same bound PROPAGATED stage by stage (`stage`, `resample`): an input known to e gives the contraction
-sum|w| e more, scale / shift add two fp32 roundings, and each stored stage adds UNIT (|value| + its error) + 2^-24."""
+sum|w| e more, scale / shift add two fp32 roundings, and each stored stage adds UNIT (|value| + its error) + 2^-24.
+
+fp32 storage has UNIT = 2^-24.  Throughout, ONE fp32 rounding is charged E32 = 2^-23 of the magnitude it rounds - twice the unit
+roundoff: it covers a matrix core that truncates where the vector ALU rounds to nearest, and the second-order terms of the products of
+(1 + delta) factors, so the counts below are plain counts of operations."""
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from tests import _resize_ref as R
 
-UNIT = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
+UNIT = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8, torch.float32: 2.0 ** -24}
 E32, TINY = 2.0 ** -23, 2.0 ** -24
 
 
@@ -161,3 +166,209 @@ class For:
 
     def _argmax_inputs(self, case, seed):
         return _argmax_inputs(self.dtype, case, seed)
+
+
+# =========================================================================================================================================
+# The training backward kernels.  References are fp64 on the CPU on operands already rounded to the storage type; every bound counts the
+# roundings the kernel performs (E32 each, see the header) on the magnitudes they round.
+# =========================================================================================================================================
+WGRAD_P_MAX = 2048                      # P^2 2^-23 << 1: one lost pixel of a P-pixel contraction stands out of a bound of P roundings
+WGRAD_SLAB_MIN_PIXELS, WGRAD_BCH = 256, 64                 # csrc/wgrad.hip: SLAB_MIN_PIXELS, BCH
+WGRAD_KC = {torch.float32: 64, torch.bfloat16: 128}        # csrc/wgrad.hip: Chunk<T>::KC, pixels staged per iteration
+WGRAD_TARGET_BLOCKS = 1024                                 # wgrad_prepare's target_blocks of a single launch
+WORKSPACE_BYTES, WS_COUNTER_BYTES = 16 << 20, 65536        # kernels.WORKSPACE_BYTES, kernels.WS_COUNTER_BYTES
+
+
+def conv_out_hw(H, W, k, stride, pad):
+    if pad < 0:                                                                # FactorizedReduce's second branch convolves x[:, :, 1:, 1:]
+        return (H + pad - k) // stride + 1, (W + pad - k) // stride + 1
+    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+
+def wgrad_slabs(M, cout, cin, taps, dtype, blocks_wanted=WGRAD_TARGET_BLOCKS, ws_bytes=0):
+    """wgrad_prepare's slab rule (csrc/wgrad.hip) restated: (number of pixel slabs = gridDim.x, pixels per slab).  ws_bytes > 0: the
+    bit-reproducible mode, where the partial tiles must fit the workspace in front of its arrival counters."""
+    kc = WGRAD_KC[dtype]
+    other = -(-cout // WGRAD_BCH) * -(-cin // WGRAD_BCH) * taps
+    slabs = -(-blocks_wanted // other)
+    slabs = max(1, min(slabs, -(-M // max(kc, WGRAD_SLAB_MIN_PIXELS))))
+    slab = -(-(-(-M // slabs)) // kc) * kc
+    if ws_bytes > WS_COUNTER_BYTES and other * 4 <= WS_COUNTER_BYTES:
+        fit = (ws_bytes - WS_COUNTER_BYTES) // (WGRAD_BCH * WGRAD_BCH * 4) // other
+        if fit >= 1 and slabs > fit:
+            slabs = fit
+            slab = -(-(-(-M // slabs)) // kc) * kc
+    return -(-M // slab), slab
+
+
+def wgrad_max_slabs(M):
+    """no launch, single or grouped, splits M pixels into more slabs than this (wgrad_prepare's max_slabs)"""
+    return -(-M // WGRAD_SLAB_MIN_PIXELS)
+
+
+def wgrad_ksplits(cout, cin):
+    """the pixel splits of the narrow tiles (csrc/wgrad.hip `ksplit`, atomics mode): the set over the 64 x 64 channel tiles of a problem"""
+    def narrow(c):
+        return [c - t * WGRAD_BCH <= 32 for t in range(-(-c // WGRAD_BCH))]
+    return {(2 if a else 1) * (2 if b else 1) for a in narrow(cout) for b in narrow(cin)}
+
+
+def _cols(x, k, stride, pad):
+    """im2col: (N, C k k, Ho Wo), zero outside the image"""
+    if pad < 0:
+        x, pad = x[:, :, -pad:, -pad:], 0
+    return F.unfold(x, k, padding=pad, stride=stride)
+
+
+def wgrad_ref(x, dy, k, stride, pad):
+    """fp64 weight gradient [Cout][Cin][R][S] of conv(x) for the output gradient dy, the same contraction on absolute values, and P[r][s],
+    the number of output pixels whose tap (r, s) lands inside the image (as a (1, 1, R, S) tensor)"""
+    N, cout = dy.shape[:2]
+    cin = x.shape[1]
+    a = dy.reshape(N, cout, -1)
+    cols = _cols(x, k, stride, pad)
+    assert cols.shape[2] == a.shape[2], (tuple(cols.shape), tuple(a.shape))
+    ref = torch.einsum("nol,nkl->ok", a, cols).view(cout, cin, k, k)
+    mag = torch.einsum("nol,nkl->ok", a.abs(), cols.abs()).view(cout, cin, k, k)
+    P = _cols(torch.ones(N, 1, x.shape[2], x.shape[3], dtype=torch.float64), k, stride, pad).sum((0, 2)).view(1, 1, k, k)
+    return ref, mag, P
+
+
+def wgrad_bound(mag, P, S, base=None, p_max=WGRAD_P_MAX):
+    """dw (fp32 in both dtypes) = base + sum_m dy x, per element:
+        |got - ref| <= (P + S + 1) 2^-23 sum_m |dy x| + S 2^-23 |base| + 2^-24
+    P accumulator roundings: one per pixel whose tap lands inside the image, what a serial fp32 accumulation performs (a masked pixel
+    adds an exact zero; the products of bf16 operands are exact in fp32).  The matrix cores add several pixels per instruction - two in
+    the fp32 MFMA, sixteen in the bf16 one - and are taken to round no more often than once per product added; E32 per rounding leaves
+    room for one that truncates.  S roundings for the one atomic or ordered add per slab, on the running sum and on what the gradient
+    tensor held (`base`); one spare for the narrow tiles' pixel shares meeting in the atomics.  The fp32 kernel in split mode
+    (fs_set_fp32_split(1), the default) contracts three-way bf16 splits of the operands and drops only the low x low partial products,
+    2^-32 of |dy x| each: inside the bound, no term of its own (its eight MFMAs per 16 pixels update the accumulator eight times per 16
+    pixels, fewer than once per pixel).
+    The bound is only as sharp as P^2 2^-23 is small: P <= p_max is asserted (p_max=None for a caller that knows and says why)."""
+    assert p_max is None or float(P.max()) <= p_max, "P = %d: a lost pixel would hide in the bound" % int(P.max())
+    b = (P + S + 1) * E32 * mag + TINY
+    if base is not None:
+        b = b + S * E32 * base.abs()
+    return b
+
+
+def dgrad_s2_ref(x_shape, w, dy, stride, pad):
+    """fp64 data gradient of the stride-2 convolution, the same contraction on absolute values, and K per element: the taps that meet a
+    real pixel for the element's output-parity class (1 / 2 / 2 / 4 of 9 for a 3x3; the largest count over the class, a border pixel's
+    missing taps add exact zeros) times Cout.  Classes without any tap have K = 0."""
+    def back(w_, dy_):
+        x0 = torch.zeros(x_shape, dtype=torch.float64, requires_grad=True)
+        conv64(x0, w_, stride, pad).backward(dy_)
+        return x0.grad
+    ref, mag = back(w, dy), back(w.abs(), dy.abs())
+    cnt = back(torch.ones_like(w[:1, :1]).expand(1, x_shape[1], -1, -1).contiguous(), torch.ones_like(dy[:, :1]))[:, :1]
+    K = torch.zeros_like(cnt)
+    for a in range(2):
+        for b in range(2):
+            cls = cnt[:, :, a::2, b::2]
+            if cls.numel():
+                K[:, :, a::2, b::2] = float(cls.max())
+    return ref, mag, K * w.shape[0]
+
+
+def cand_range(in_size, out_size):
+    """csrc/resize.hip cand_range restated in fp32: per input index i the output range [lo, hi] the backward gather visits"""
+    f = np.float32
+    scale = f(in_size - 1) / f(out_size - 1) if out_size > 1 else f(0)
+    i = np.arange(in_size)
+    if scale <= 0:
+        return np.zeros(in_size, dtype=np.int64), np.full(in_size, out_size - 1, dtype=np.int64)
+    inv = f(1) / scale
+    lo = np.floor((i - 1).astype(f) * inv).astype(np.int64) - 1
+    hi = np.ceil((i + 1).astype(f) * inv).astype(np.int64) + 1
+    return np.clip(lo, 0, None), np.clip(hi, None, out_size - 1)
+
+
+def tap_matrix(in_size, out_size):
+    """(out, in) fp64 matrix of the forward's tap weights, tests/_resize_ref.taps: w[o][i] = l0 [i0 == i] + l1 [i1 == i]"""
+    i0, i1, l0, l1 = R.taps(in_size, out_size)
+    w = torch.zeros(out_size, in_size, dtype=torch.float64)
+    o = torch.arange(out_size)
+    w[o, torch.from_numpy(i0).long()] += torch.from_numpy(l0)
+    w[o, torch.from_numpy(i1).long()] += torch.from_numpy(l1)
+    return w
+
+
+def near_matrix(in_size, out_size):
+    """(out, in) 0 / 1: output o lies in the widened candidate range of input i"""
+    lo, hi = cand_range(in_size, out_size)
+    o = np.arange(out_size)[:, None]
+    return torch.from_numpy(((o >= lo[None, :]) & (o <= hi[None, :])).astype(np.float64))
+
+
+def resample_bwd(dtype, dy, yo, in_hw, relu, extra=0):
+    """bilinear backward dx[i] = sum_o w(o, i) g[o], g = dy [y_out > 0] (N, C, Ho, Wo fp64) -> (ref, bound), (N, C, Hi, Wi):
+        (n_o + 2 + extra) 2^-23 sum_o |w g|  +  2^-24 (Hi + Wi) sum_{o near i} |g[o]|  +  UNIT (|ref| + the above)  +  2^-24
+    n_o contributing outputs: per output the product wh * ww, the product with g and the accumulation, n_o + 2 roundings on sum |w g|
+    (`extra` = 1 for the separable NCHW form, which rounds the row pass's intermediate once more).  The second term is the weight
+    uncertainty `_resample` documents: make_tap may be contracted into an fma, so a weight - or the pixel a near-integer tap is attributed
+    to - moves by at most half an ulp of the source coordinate, 2^-24 * in_size per axis, at any output the gather visits ("near": the
+    widened candidate range of i).  Then one store in `dtype`."""
+    hi_, wi_ = in_hw
+    g = dy * (yo > 0).double() if relu else dy
+    wh, ww = tap_matrix(hi_, dy.shape[2]), tap_matrix(wi_, dy.shape[3])
+    ref = torch.einsum("ah,ncab,bw->nchw", wh, g, ww)
+    mag = torch.einsum("ah,ncab,bw->nchw", wh, g.abs(), ww)
+    near = torch.einsum("ah,ncab,bw->nchw", near_matrix(hi_, dy.shape[2]), g.abs(), near_matrix(wi_, dy.shape[3]))
+    n_o = (wh > 0).sum(0).double()[:, None] * (ww > 0).sum(0).double()[None, :]
+    e = (n_o + 2 + extra) * E32 * mag + TINY * (hi_ + wi_) * near
+    return ref, e + UNIT[dtype] * (ref.abs() + e) + TINY
+
+
+BN_BWD_ROUNDINGS = 9
+
+
+def bn_bwd(dtype, z, dy, yo, mean, invstd, gamma, relu, dg_acc=None, db_acc=None):
+    """BatchNorm(+ReLU) backward on its own inputs: z, dy, y_out (G, n, C) fp64 values of `dtype`, the GIVEN fp32 mean / invstd (G, C)
+    and gamma (C).  g = dy [y_out > 0], xh = (z - mu) is, A0 = sum g, A1 = sum g xh, dz = gamma is (g - A0 / n - xh A1 / n).
+      eA0 = n 2^-23 sum|g|, eA1 = (n + 3) 2^-23 sum|g xh|: n - 1 additions in any order (wave shuffles, LDS in wave order, block
+        partials, atomics), the product, and the two roundings of xh (subtraction, product).
+      dz: c = 9 fp32 roundings at most on any term - xh 2, 1 / n 1, xh * A1 * (1 / n) 2, the two subtractions 2, gamma * is and the
+        product with it 2 (the A0 term carries 6 of them, g 4) - plus the reductions' errors through 1 / n, then one store:
+        |gamma is| [c 2^-23 (|g| + |A0| / n + |xh A1| / n) + (eA0 + |xh| eA1) / n]  +  UNIT (|ref| + that)  +  2^-24.
+      dbeta = sum_G A0, dgamma = sum_G A1: the groups' eA plus one rounding per group total added (G 2^-23 sum_G |A|); accumulators
+        given: 2^-23 (|acc| + |ref|) more, and the reference is acc + the sum.
+    Returns dict(dz, dz_bound, dbeta, dbeta_bound, dgamma, dgamma_bound)."""
+    G, n, C = z.shape
+    g = dy * (yo > 0).double() if relu else dy
+    mu, is_ = mean[:, None, :], invstd[:, None, :]
+    xh = (z - mu) * is_
+    a0, a1 = g.sum(1, keepdim=True), (g * xh).sum(1, keepdim=True)
+    e0, e1 = n * E32 * g.abs().sum(1, keepdim=True), (n + 3) * E32 * (g * xh).abs().sum(1, keepdim=True)
+    k = (gamma.view(1, 1, C) * is_)
+    ref = k * (g - a0 / n - xh * a1 / n)
+    e = k.abs() * (BN_BWD_ROUNDINGS * E32 * (g.abs() + a0.abs() / n + (xh * a1).abs() / n) + (e0 + xh.abs() * e1) / n)
+    out = dict(dz=ref, dz_bound=e + UNIT[dtype] * (ref.abs() + e) + TINY)
+    for name, a, ea, acc in (("dbeta", a0, e0, db_acc), ("dgamma", a1, e1, dg_acc)):
+        tot = a.sum(0).view(C)
+        b = ea.sum(0).view(C) + G * E32 * a.abs().sum(0).view(C) + TINY
+        out[name], out[name + "_bound"] = tot, b
+        if acc is not None:
+            out[name + "_acc"], out[name + "_acc_bound"] = acc + tot, b + E32 * (acc.abs() + tot.abs())
+    return out
+
+
+def bn_operands(dtype, G, n, C, relu, seed):
+    """operands of a BatchNorm backward: z with a non-zero mean, the saved statistics computed in fp64 and rounded ONCE to fp32"""
+    z = rnd16(dtype, G, n, C, seed=seed).mul(1.5).add(0.3).to(dtype).double()
+    dy = rnd16(dtype, G, n, C, seed=seed + 1)
+    g = torch.Generator().manual_seed(seed + 2)
+    gamma = (torch.randn(C, generator=g).abs() + 0.5).double()
+    beta = (torch.randn(C, generator=g) * 0.2).double()
+    mean = z.mean(1).float().double()
+    invstd = (1.0 / torch.sqrt(z.var(1, unbiased=False) + 1e-5)).float().double()
+    y = gamma * (z - mean[:, None]) * invstd[:, None] + beta
+    yo = (F.relu(y) if relu else y).to(dtype).double()
+    return z, dy, yo, mean, invstd, gamma
+
+
+def old_bars(err, ref):
+    """how many elements the three older bars flag: 2e-2 max|ref|, 2e-4 max|ref| + 1e-4, 1e-4 + 1e-4 |ref|"""
+    m = float(ref.abs().max())
+    return int((err > 2e-2 * m).sum()), int((err > 2e-4 * m + 1e-4).sum()), int((err > 1e-4 + 1e-4 * ref.abs()).sum())

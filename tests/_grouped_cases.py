@@ -363,8 +363,22 @@ class GradBuffer:
         self.base = rnd(*shape, seed=seed).float()
         self.want = torch.zeros(shape, dtype=torch.float64)
         self.mask = torch.zeros(shape, dtype=torch.bool)
+        self.mag = torch.zeros(shape, dtype=torch.float64)         # sum over the contributors of sum_m |dy x|
+        self.parts = []                                            # per contributor: (its sum_m |dy x| placed like `want`, P likewise, slabs)
         self.who = []
         self.reset()
+
+    def bound(self):
+        """tests/_bounds.wgrad_bound per contributor, summed: each problem adds onto the random base and whatever the others left, so its
+        `base` is |base| + the others' magnitudes.  The slab count is the most any launch makes of M pixels (the grouped launch asks every
+        problem for its share of the blocks: fewer slabs, never more).  #2 of the table contracts 6039 pixels, beyond the 2048 up to which
+        the bound resolves a single lost pixel: it is held to the bound all the same (p_max=None), which still is orders of magnitude
+        below the tensor-wide bar."""
+        from tests import _bounds as B
+        total = torch.zeros_like(self.mag)
+        for mag, P, S in self.parts:
+            total += B.wgrad_bound(mag, P, S, self.base.double().abs() + self.mag - mag, p_max=B.WGRAD_P_MAX if float(P.max()) <= B.WGRAD_P_MAX else None)
+        return total
 
     def reset(self):
         self.dev = self.base.clone().to(DEVICE)
@@ -379,6 +393,8 @@ class GradBuffer:
         tol = 2e-4 * scale + 1e-4 if dtype == F32 else 2e-2 * scale          # test_conv2d_dgrad_and_wgrad
         err = float((delta - self.want)[self.mask].abs().max())
         assert err <= tol, "%s: wgrad max err %.3e vs max|ref| %.3e (tol %.3e)" % (what, err, scale, tol)
+        from tests import _bounds as B
+        B.assert_within(delta[self.mask], self.want[self.mask], self.bound()[self.mask], what + " per element")
         return err
 
 
@@ -394,6 +410,10 @@ class WgradProblem:
         w0 = torch.zeros(Cout, Cin, k, k, dtype=torch.float64, requires_grad=True)
         ref_conv(x, w0, stride, pad).backward(dy)
         grad = w0.grad                                                           # [Cout][Cin][R][S]
+        from tests import _bounds as B
+        ref, mag, P = B.wgrad_ref(x, dy, k, stride, pad)
+        assert torch.allclose(ref, grad, rtol=1e-12, atol=1e-12)
+        P = P.expand_as(mag)
         self.x = Slab(N * H * W, Cin, dtype, cs=spec.get("x_cs"), data=to_pix(x))
         dy_cs = spec.get("dy_cs")
         self.dy = Slab(N * Ho * Wo, Cout, dtype, cs=dy_cs, c0=(dy_cs - Cout) // 8 * 8 if dy_cs else 0, data=to_pix(dy))
@@ -410,14 +430,21 @@ class WgradProblem:
         self.buffer = buffers[name]
         assert tuple(self.buffer.base.shape) == shape
         self.buffer.who.append(tag)
+        mag_b, P_b = torch.zeros(shape, dtype=torch.float64), torch.zeros(shape, dtype=torch.float64)
         for t in range(shape[0]):
             g = grad[t * rows:(t + 1) * rows]
             if orsi:
                 self.buffer.want[t, :rows, :, :, :Cin] += g.permute(0, 2, 3, 1)
                 self.buffer.mask[t, :rows, :, :, :Cin] = True
+                mag_b[t, :rows, :, :, :Cin] = mag[t * rows:(t + 1) * rows].permute(0, 2, 3, 1)
+                P_b[t, :rows, :, :, :Cin] = P[t * rows:(t + 1) * rows].permute(0, 2, 3, 1)
             else:
                 self.buffer.want[t, :rows, :Cin] += g
                 self.buffer.mask[t, :rows, :Cin] = True
+                mag_b[t, :rows, :Cin] = mag[t * rows:(t + 1) * rows]
+                P_b[t, :rows, :Cin] = P[t * rows:(t + 1) * rows]
+        self.buffer.mag += mag_b
+        self.buffer.parts.append((mag_b, P_b, B.wgrad_max_slabs(N * Ho * Wo)))
         self.strides = (k * k * I, 1, I) if orsi else (I * k * k, k * k, 1)      # elements between O rows, I columns, taps
         if pair:
             self.desc.n_seg, self.desc.g_jump = rows, O - rows
