@@ -115,6 +115,8 @@ SIGNATURES = {
     "fs_conv_stem_u8_infer_fwd": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int] + [c_float] * 6,
     "fs_bilinear_fwd": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp],
     "fs_bilinear_argmax": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp],
+    "fs_bilinear_argmax_conf": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp, c_vp, c_int, c_int],
+    "fs_score_confidence": [c_vp, c_vp, c_ll, c_int, c_int, c_vp, c_vp, c_int, c_int],
     "fs_hist_info": [c_vp, c_vp, c_vp, c_int, c_ll, c_int, c_vp, c_vp],
     "fs_heads_confusion": [c_vp, ctypes.POINTER(HeadsDesc), c_vp, c_vp, c_int, c_vp, c_vp],
     "fs_eval_window_input": [c_vp, ctypes.POINTER(EvalWindowDesc), c_vp, c_vp, c_vp, c_vp],

@@ -68,7 +68,14 @@ class _Tracer:
 
 class InferenceEngine:
     def __init__(self, net, input_shape, dtype=torch.bfloat16, logits_dtype=torch.float32, device="cuda", use_graph=True,
-                 halo_min_pixels=16384, lanes=3, fuse_cells=None, output="logits", input="float", image_mean=None, image_std=None):
+                 halo_min_pixels=16384, lanes=3, fuse_cells=None, output="logits", input="float", image_mean=None, image_std=None,
+                 min_confidence=None, ignore_label=None):
+        # "classes+confidence" only: the class map holds `ignore_label` where the confidence byte is below
+        # kernels.confidence_threshold(min_confidence).  Refused with any other output, and for an invalid value, before anything else
+        if output != "classes+confidence" and (min_confidence is not None or ignore_label is not None):
+            raise ValueError("min_confidence / ignore_label belong to output='classes+confidence', got output=%r" % (output,))
+        self.min_conf = K.confidence_threshold(0.0 if min_confidence is None else min_confidence)
+        self.ignore_label = K._check_ignore_label(255 if ignore_label is None else ignore_label)
         assert not net.training, "call net.eval() first"
         # "float": `self.input` is the normalised fp32 NCHW image; "uint8": it is the uint8 (N, H, W, 3) RGB frame and the stem normalises
         # while it stages the image (fs_conv_stem_u8_fwd: ((float)u / 255 - image_mean[c]) / image_std[c])
@@ -96,7 +103,9 @@ class InferenceEngine:
         # launch, so a validation frame writes 2 MB instead of 159 MB
         # "lowres": the head's logits before the final up-sample, as an NHWC view (N, C, h, w) - for consumers that evaluate
         # the bilinear up-sample themselves (losses.distill_kl_lowres reads the teacher this way)
-        assert output in ("logits", "classes", "lowres")
+        # "classes+confidence": (classes, confidence), both uint8 (N, H, W) - the class map of "classes" and, from the same launch
+        # (fs_bilinear_argmax_conf), the byte floor(255 p + 0.5) of the winning class's softmax probability at every pixel
+        assert output in ("logits", "classes", "lowres", "classes+confidence")
         self.output_mode = output
         self.vec = K.vec_of(dtype)
         # 3x3/s1 layers with at least this many output pixels run on the LDS-halo kernel (conv3x3_halo.hip)
@@ -416,11 +425,13 @@ class InferenceEngine:
             if out.storage is not None or op.get("dead"):
                 continue
             N, C, H, W = out.shape
-            if out.nchw and self.output_mode == "classes":
+            if out.nchw and self.output_mode in ("classes", "classes+confidence"):
                 t = torch.empty((N, H, W), dtype=torch.uint8, device=self.device)
                 self._keep.append(t)
                 self.buffers["out%d" % idx] = t
                 out.storage = ("out%d" % idx, 0)
+                if self.output_mode == "classes+confidence":
+                    self.confidence = torch.empty((N, H, W), dtype=torch.uint8, device=self.device)
                 continue
             if out.nchw:
                 t = torch.empty((N, C, H, W), dtype=self.logits_dtype, device=self.device)
@@ -435,6 +446,13 @@ class InferenceEngine:
         self.output = self.buffers[self.out_sym.storage[0]]
         if self.output_mode == "lowres":
             self.output = self.output.permute(0, 3, 1, 2)[:, :self.out_sym.shape[1]]
+        if self.output_mode == "classes+confidence":
+            self.output = (self.output, self.confidence)
+            # the NHWC (N, C, h, w) view of the buffer the final launch reads (valid after a run): what a host reference of the
+            # confidence starts from
+            head = self.ops[self.out_sym.producer]["x"]
+            bid, off = head.storage
+            self.head_logits = self.buffers[bid].permute(0, 3, 1, 2)[:, off:off + head.shape[1]]
 
     def _ptr(self, sym):
         bid, off = sym.storage
@@ -737,7 +755,12 @@ class InferenceEngine:
                 d = ResizeDesc(N, Hi, Wi, Ho, Wo, C, x_cs, y_cs, K.dtype_code(self.dtype), int(op["relu"]), onchw)
                 self._keep.append(d)
                 args = (ctypes.byref(d), ctypes.c_void_p(xp), ctypes.c_void_p(yp))
-                if op["out_nchw"] and self.output_mode == "classes":
+                if op["out_nchw"] and self.output_mode == "classes+confidence":
+                    args += (ctypes.c_void_p(self.confidence.data_ptr()), self.min_conf, self.ignore_label)
+                    self.calls.append(dict(fn="fs_bilinear_argmax_conf", args=args, desc=d, family="resize_argmax_conf", flops=0.0,
+                                           bytes=es * N * Hi * Wi * C + 2 * N * Ho * Wo,
+                                           label="resize %dx%d->%dx%d C%d + argmax + confidence -> 2 x uint8" % (Hi, Wi, Ho, Wo, C)))
+                elif op["out_nchw"] and self.output_mode == "classes":
                     self.calls.append(dict(fn="fs_bilinear_argmax", args=args, desc=d, family="resize_argmax", flops=0.0,
                                            bytes=es * N * Hi * Wi * C + N * Ho * Wo,
                                            label="resize %dx%d->%dx%d C%d + argmax -> uint8" % (Hi, Wi, Ho, Wo, C)))
@@ -1295,7 +1318,9 @@ class InferenceEngine:
         self.graph, self.graph_lanes, self._side_streams = best[1], best[2], best[3]
         # the same plan issued directly from the C executor (no hipGraph): cheaper on the host per launch
         self.use_program = False
-        if bool(int(os.environ.get("FS_ENGINE_PROGRAM", "1"))):
+        # (a plan with a launch the executor has no command for - fs_bilinear_argmax_conf: the command list is part of the ABI and
+        # closed at FS_OP_STEM_U8 - is issued by its graph)
+        if bool(int(os.environ.get("FS_ENGINE_PROGRAM", "1"))) and all(c["fn"] in self._OPS for c in self.calls):
             self._build_program()
             for _ in range(5):
                 self._run_program()
@@ -1311,7 +1336,8 @@ class InferenceEngine:
             self.use_program = ms < best[0]
 
     def run(self):
-        """One forward on the current contents of `self.input`; result in `self.output` (contiguous NCHW logits)."""
+        """One forward on the current contents of `self.input`; result in `self.output` (contiguous NCHW logits; the class map, the
+        low-resolution view or the (classes, confidence) pair in the other output modes)."""
         if getattr(self, "use_program", False):
             self._run_program()
         elif self.graph is not None:

@@ -31,6 +31,7 @@ class _ImageState:
         self.img = torch.empty((H, W, 3), dtype=torch.uint8, device=device)
         self.total = torch.empty((H, W, cs), dtype=torch.float32, device=device)
         self.classes = torch.empty((H, W), dtype=torch.uint8, device=device)
+        self.conf = torch.empty((H, W), dtype=torch.uint8, device=device)       # predict(): the confidence byte beside the class map
         self.canvas = torch.empty(0, dtype=torch.float32, device=device)
         self.plans = {}
         self.outputs = {}
@@ -61,6 +62,7 @@ class SegEvaluator:
         # process_image, no fp32 image; the flip, padded and multi-scale paths resample and keep fs_eval_window_input
         self.uint8_input = bool(uint8_input)
         self._u8_engines = {}                       # (H, W) -> uint8 "classes" engine
+        self._conf_engines = {}                     # predict(): (H, W, uint8 input, min_conf byte, ignore_label) -> "classes+confidence" engine
         self.engine = None
         if len(self.multi_scales) == 1 and not self.is_flip:
             self.engine = self._u8_engine(H, W) if self.uint8_input else \
@@ -87,6 +89,7 @@ class SegEvaluator:
             network = network.eval()
         engines = ([self.engine] if self.engine is not None else []) + list(self._lowres.values())
         engines += [e for e in self._u8_engines.values() if e is not self.engine]
+        engines += list(self._conf_engines.values())
         for eng in engines:
             eng.load_weights(network)
         if network is not None:
@@ -110,6 +113,15 @@ class SegEvaluator:
         if eng is None:
             eng = self._u8_engines[(H, W)] = engine.InferenceEngine(self.val_func, (1, 3, H, W), dtype=self.dtype, output="classes",
                                                                     input="uint8", image_mean=self._mean, image_std=self._std)
+        return eng
+
+    def _conf_engine(self, H, W, min_confidence, ignore_label):
+        key = (H, W, self.uint8_input, K.confidence_threshold(min_confidence), K._check_ignore_label(ignore_label))
+        eng = self._conf_engines.get(key)
+        if eng is None:
+            kw = dict(input="uint8", image_mean=self._mean, image_std=self._std) if self.uint8_input else {}
+            eng = self._conf_engines[key] = engine.InferenceEngine(self.val_func, (1, 3, H, W), dtype=self.dtype, output="classes+confidence",
+                                                                   min_confidence=min_confidence, ignore_label=ignore_label, **kw)
         return eng
 
     # ---- device buffers and engines of the multi-scale / flip paths ------------------------------------------------------
@@ -225,6 +237,55 @@ class SegEvaluator:
         for i, p in enumerate(plans):
             self.scale_process(img, p, store=(i == 0), classes=st.classes if i == len(plans) - 1 else None)
         return st.classes
+
+    def predict(self, img, min_confidence=0.0, ignore_label=255, output_size=None, input_size=None):
+        """The class map AND the per-pixel confidence of the configured mode: (classes, confidence), both uint8 (H, W) on the device.
+        confidence = floor(255 conf + 0.5) with conf the share of the winning class in the mode's score (exp(logit), summed over the
+        scales and flips the mode has); classes holds `ignore_label` where that byte is below kernels.confidence_threshold(
+        min_confidence), and with min_confidence=0 it is the map whole_eval / sliding_eval return for the same image.
+        One scale without flip, padding or output_size: a "classes+confidence" engine, built on first use and kept (one launch,
+        fs_bilinear_argmax_conf, writes both maps); flip / input_size / output_size: the score canvas, then fs_score_confidence;
+        several scales: fs_score_confidence on the image's summed total after the last scale.  The maps are buffers that the next
+        call with the same image shape overwrites."""
+        K.confidence_threshold(min_confidence), K._check_ignore_label(ignore_label)
+        if len(self.multi_scales) > 1:
+            assert output_size is None and input_size is None, "output_size / input_size belong to the single-scale mode"
+            img, st = self._upload(img)
+            H, W = int(img.shape[0]), int(img.shape[1])
+            plans = self._plan(st, H, W, self.crop_size, self.stride_rate)
+            for i, p in enumerate(plans):
+                self.scale_process(img, p, store=(i == 0))
+            return K.score_confidence(st.total, self.class_num, min_confidence, ignore_label, classes=st.classes, conf=st.conf)
+        if output_size is None and input_size is None and not self.is_flip:
+            # (one engine per image shape, threshold byte and ignore label: they are arguments of the engine's captured final launch)
+            x = self._upload(img)[0] if self.uint8_input else self.process_image(img)
+            H, W = (int(v) for v in (x.shape[:2] if self.uint8_input else x.shape[2:]))
+            classes, conf = self._conf_engine(H, W, min_confidence, ignore_label)(x)
+            return classes[0], conf[0]
+        img, st = self._upload(img)
+        H, W = int(img.shape[0]), int(img.shape[1])
+        ih, iw = EP.two_d(input_size) if input_size is not None else (H, W)
+        top, bottom, left, right = EP.pad_margins(H, W, ih, iw)
+        PH, PW = H + top + bottom, W + left + right
+        flip = self.is_flip
+        eng = self._lowres_engine((2 if flip else 1, 3, PH, PW))
+        ytab, xtab = self._identity_taps(st, H, W)
+        d = K.eval_window_desc(H, W, H, W, top, left, 0, 0, PH, PW, EP.PAD_NORMALISED, flip, self._mean, self._std)
+        K.eval_window_input(d, img, ytab, xtab, eng.input)
+        canvas = self._canvas(st, H, W)
+        K.eval_score_accumulate(eng.run(), (PH, PW), flip, (top, left, H, W), canvas=canvas, store=True)
+        if output_size is None:
+            return K.score_confidence(canvas, self.class_num, min_confidence, ignore_label, classes=st.classes, conf=st.conf)
+        OH, OW = EP.two_d(output_size)
+        out = st.outputs.get((OH, OW))
+        if out is None:
+            out = st.outputs[(OH, OW)] = (torch.empty((OH, OW, self.cs), dtype=torch.float32, device=self.device),
+                                          torch.empty((OH, OW), dtype=torch.uint8, device=self.device))
+        cout = st.outputs.get(("conf", OH, OW))
+        if cout is None:
+            cout = st.outputs[("conf", OH, OW)] = torch.empty((OH, OW), dtype=torch.uint8, device=self.device)
+        K.eval_rescale_accumulate(canvas, self.class_num, (0, 0, H, W), out[0], store=True)
+        return K.score_confidence(out[0], self.class_num, min_confidence, ignore_label, classes=out[1], conf=cout)
 
     def func_per_iteration(self, data):
         """data: {'data': HWC uint8 image, 'label': (H, W) labels}; accumulates on the device, returns the class map.

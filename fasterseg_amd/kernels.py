@@ -436,6 +436,70 @@ def bilinear(x, size, relu=False, out=None, out_nchw=0, channels=None):
     return out
 
 
+def _logits_resize_desc(x, size):
+    x_cs = channel_stride(x)
+    assert x_cs is not None, "logits must be an NHWC view"
+    N, C, Hi, Wi = x.shape
+    return ResizeDesc(N, Hi, Wi, int(size[0]), int(size[1]), C, x_cs, 0, dtype_code(x.dtype), 0, 0)
+
+
+def _u8_map(t, shape, device, what):
+    if t is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    assert t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == tuple(shape), "%s: a contiguous uint8 %s" % (what, tuple(shape))
+    return t
+
+
+def bilinear_argmax(x, size, classes=None):
+    """fs_bilinear_argmax: NHWC logits view (N, C, h, w) -> uint8 (N, Ho, Wo) arg-max of the align_corners=True up-sample to `size`."""
+    d = _logits_resize_desc(x, size)
+    classes = _u8_map(classes, (d.N, d.Ho, d.Wo), x.device, "classes")
+    call("fs_bilinear_argmax", _stream(), ctypes.byref(d), _p(x), _p(classes))
+    return classes
+
+
+def confidence_threshold(t):
+    """min_confidence in [0, 1] -> the byte the kernels compare with: ceil(255 t) (0 -> 0: nothing is masked, 0.9 -> 230, 1 -> 255; the
+    float product, so that k / 255 gives k for every byte k)."""
+    import math
+    t = float(t)
+    if not 0.0 <= t <= 1.0:        # a NaN fails both comparisons
+        raise ValueError("min_confidence must be in [0, 1], got %r" % (t,))
+    return int(math.ceil(255.0 * t))
+
+
+def _check_ignore_label(ignore_label):
+    if isinstance(ignore_label, bool) or int(ignore_label) != ignore_label or not 0 <= int(ignore_label) <= 255:
+        raise ValueError("ignore_label must be an integer in 0..255, got %r" % (ignore_label,))
+    return int(ignore_label)
+
+
+def bilinear_argmax_conf(x, size, min_confidence=0.0, ignore_label=255, classes=None, conf=None):
+    """fs_bilinear_argmax_conf: NHWC logits view (N, C, h, w) -> (classes, conf), both uint8 (N, Ho, Wo): the arg-max of the up-sample with
+    `ignore_label` where the confidence byte is below confidence_threshold(min_confidence), and the byte q = floor(255 p + 0.5) of the
+    winner's softmax probability.  classes=False / conf=False: that map is not written (None is returned in its place)."""
+    d = _logits_resize_desc(x, size)
+    mc, ig = confidence_threshold(min_confidence), _check_ignore_label(ignore_label)
+    shape = (d.N, d.Ho, d.Wo)
+    classes = None if classes is False else _u8_map(classes, shape, x.device, "classes")
+    conf = None if conf is False else _u8_map(conf, shape, x.device, "conf")
+    call("fs_bilinear_argmax_conf", _stream(), ctypes.byref(d), _p(x), _p(classes), _p(conf), mc, ig)
+    return classes, conf
+
+
+def score_confidence(score, C, min_confidence=0.0, ignore_label=255, classes=None, conf=None):
+    """fs_score_confidence on a contiguous fp32 score buffer (..., cs) of summed exp-scores: per pixel the first maximum over the first C
+    channels and its share of their sum as a byte -> (classes, conf), uint8 of shape score.shape[:-1].  classes=False / conf=False as in
+    bilinear_argmax_conf."""
+    assert score.dtype == torch.float32 and score.is_contiguous() and score.dim() >= 2
+    mc, ig = confidence_threshold(min_confidence), _check_ignore_label(ignore_label)
+    shape = tuple(score.shape[:-1])
+    classes = None if classes is False else _u8_map(classes, shape, score.device, "classes")
+    conf = None if conf is False else _u8_map(conf, shape, score.device, "conf")
+    call("fs_score_confidence", _stream(), _p(score), score.numel() // score.shape[-1], int(score.shape[-1]), int(C), _p(classes), _p(conf), mc, ig)
+    return classes, conf
+
+
 def bilinear_bwd(dy, y_out, in_shape, relu, dtype, out_nchw=0, dx_cs=None):
     """Gradient w.r.t. the input of `bilinear`; dy NHWC (or contiguous NCHW fp32 when out_nchw)."""
     N, C, Hi, Wi = in_shape

@@ -226,3 +226,65 @@ class SegTester(SegEvaluator):
         if self.writer is not None:
             writer, self.writer = self.writer, None
             writer.close()
+
+
+class PseudoLabeler(SegEvaluator):
+    """Pseudo-labels for unlabelled frames from a trained network (the teacher, before the student's distillation run): per frame
+    `<fn>.png` under save_dir, the single-channel train-id map with `ignore_label` wherever the winning class's confidence is below
+    `min_confidence` - the label format dataloader.py reads - and with save_confidence `<fn>.conf.png`, the confidence byte
+    floor(255 conf + 0.5).  Both maps come from SegEvaluator.predict (one launch in the single-scale mode) and go through the
+    PredictionWriter; evaluator_kwargs go to SegEvaluator.  The kept pixels are counted per class on the device (fs_hist_info of the map
+    against itself: the masked pixels carry ignore_label >= class_num and are skipped) and read back once, by run_online.
+    write=False labels every frame but writes no file."""
+
+    def __init__(self, network, class_num, image_mean, image_std, save_dir, min_confidence=0.9, ignore_label=255, save_confidence=False,
+                 slots=4, workers=4, write=True, **evaluator_kwargs):
+        self.min_conf = K.confidence_threshold(min_confidence)
+        if K._check_ignore_label(ignore_label) < class_num:
+            raise ValueError("ignore_label %d is one of the %d classes" % (ignore_label, class_num))
+        super().__init__(network, class_num, image_mean, image_std, **evaluator_kwargs)
+        self.min_confidence = min_confidence
+        self.ignore_label = int(ignore_label)
+        self.save_dir = save_dir
+        self.save_confidence = bool(save_confidence)
+        self.frames = 0
+        self.pixels = 0
+        self.writer = None
+        if write:
+            os.makedirs(save_dir, exist_ok=True)
+            self.writer = PredictionWriter(slots=slots, workers=workers, device=self.device)
+
+    def func_per_iteration(self, data):
+        """data: {'data': HWC uint8 image, 'fn': name}.  Queues the files, counts the kept pixels, returns (classes, confidence)."""
+        classes, conf = self.predict(data['data'], self.min_confidence, self.ignore_label)
+        classes = classes.contiguous()
+        H, W = int(classes.shape[0]), int(classes.shape[1])
+        if self.writer is not None:
+            outputs = [(os.path.join(self.save_dir, data['fn'] + ".png"), (H, W))]
+            if self.save_confidence:
+                outputs.append((os.path.join(self.save_dir, data['fn'] + ".conf.png"), (H, W)))
+
+            def render(views):
+                views[0].copy_(classes)
+                if self.save_confidence:
+                    views[1].copy_(conf)
+            self.writer.submit(outputs, render)
+        self.acc.add(classes, classes)
+        self.frames += 1
+        self.pixels += H * W
+        return classes, conf
+
+    def run_online(self, dataset):
+        """Every frame of an iterable of such dicts; returns when the last file is on disk: {"frames", "kept": the fraction of the
+        pixels that kept their class, "per_class": kept pixels per class (int64 array)} - one device-to-host read."""
+        for data in dataset:
+            self.func_per_iteration(data)
+        if self.writer is not None:
+            self.writer.flush()
+        hist, labeled, _ = self.acc.result()
+        return {"frames": self.frames, "kept": labeled / self.pixels if self.pixels else 0.0, "per_class": np.diag(hist).copy()}
+
+    def close(self):
+        if self.writer is not None:
+            writer, self.writer = self.writer, None
+            writer.close()

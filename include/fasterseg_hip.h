@@ -567,6 +567,25 @@ fs_status fs_kl_distill_bwd(void* stream, const float* student, const float* tea
  * x: NHWC logits with channel stride d->x_cs (a multiple of 4, >= C; pad lanes readable), d->Wo % 4 == 0; d->y_cs, d->relu
  * and d->out_nchw are ignored.  Ties: the lowest class index wins, as np.argmax. */
 fs_status fs_bilinear_argmax(void* stream, const fs_resize_desc* d, const void* x, unsigned char* classes);
+/* Per-pixel confidence next to the class map.  Two added symbols: no struct and no existing signature changed, so FS_ABI_VERSION stays
+ * 221 (as when fs_conv_stem_u8_infer_fwd arrived); a library built before them simply does not export them.
+ * The confidence of a pixel is the share of the winning class in the reference evaluator's score, exp(logit) summed over scales and
+ * flips (tools/engine/evaluator.py:297-318): conf = max_c s_c / sum_c s_c, stored as q = floor(255 conf + 0.5).  A pixel is KEPT iff
+ * q >= min_conf (0..255; 0 keeps everything); elsewhere the class map holds ignore_label (0..255).  `conf` always holds the real q.
+ * Either of `classes` / `conf` may be NULL (only the other is written), not both.
+ *
+ * fs_bilinear_argmax_conf: d and x as fs_bilinear_argmax (NHWC logits in FS_F32 / FS_BF16 / FS_F16, x_cs a multiple of 4 and
+ * >= round_up(C, 4), pad lanes readable and never part of the sum, Wo % 4 == 0).  Per output pixel the same up-sample and arg-max
+ * (first maximum wins) and conf = 1 / sum_{c<C} exp(v_c - v_max) in fp32: the softmax probability of the arg-max class.  With
+ * min_conf == 0 the class map is bit for bit fs_bilinear_argmax's.  Wo == 8 Wi (Wi >= 2, C <= 20, x_cs >= 20, 8-byte aligned outputs)
+ * takes a 1 x 8 strip kernel, everything else a generic one. */
+fs_status fs_bilinear_argmax_conf(void* stream, const fs_resize_desc* d, const void* x, unsigned char* classes, unsigned char* conf,
+                                  int min_conf, int ignore_label);
+/* The same decision on an fp32 score buffer (pixels, cs), cs % 4 == 0, 1 <= C <= cs, 16-byte aligned: the evaluator's canvas / total
+ * of summed exp-scores.  classes = the first maximum over c < C (what fs_eval_rescale_accumulate writes for the same buffer),
+ * conf = max / sum over c < C; a sum that is zero or not finite gives q = 0. */
+fs_status fs_score_confidence(void* stream, const float* score, long long pixels, int cs, int C, unsigned char* classes,
+                              unsigned char* conf, int min_conf, int ignore_label);
 /* hist_info of tools/seg_opr/metric.py:7-17 on the device: over the n pixels with 0 <= gt < n_cl,
  * hist[n_cl * gt + pred] += 1, counts[0] += 1 (labeled), counts[1] += (pred == gt) (correct).  gt is uint8 / int32 / int64
  * (gt_bytes = 1 / 4 / 8; 255 or -1 = ignore); hist (n_cl * n_cl) and counts (2) are uint64 accumulators the caller zeroes
