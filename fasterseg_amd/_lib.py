@@ -117,6 +117,9 @@ SIGNATURES = {
     "fs_bilinear_argmax": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp],
     "fs_bilinear_argmax_conf": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp, c_vp, c_int, c_int],
     "fs_score_confidence": [c_vp, c_vp, c_ll, c_int, c_int, c_vp, c_vp, c_int, c_int],
+    "fs_bilinear_argmax_conf_pc": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp, c_vp, c_vp, c_int],
+    "fs_score_confidence_pc": [c_vp, c_vp, c_ll, c_int, c_int, c_vp, c_vp, c_vp, c_int],
+    "fs_confidence_hist": [c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_int, c_vp],
     "fs_hist_info": [c_vp, c_vp, c_vp, c_int, c_ll, c_int, c_vp, c_vp],
     "fs_heads_confusion": [c_vp, ctypes.POINTER(HeadsDesc), c_vp, c_vp, c_int, c_vp, c_vp],
     "fs_eval_window_input": [c_vp, ctypes.POINTER(EvalWindowDesc), c_vp, c_vp, c_vp, c_vp],

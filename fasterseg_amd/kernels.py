@@ -474,30 +474,98 @@ def _check_ignore_label(ignore_label):
     return int(ignore_label)
 
 
-def bilinear_argmax_conf(x, size, min_confidence=0.0, ignore_label=255, classes=None, conf=None):
+def class_threshold_bytes(thresholds, class_num):
+    """Per-class thresholds -> uint8 numpy (256,), entry k for class k, entries >= class_num 0.  `thresholds`: one value or class_num
+    values; a uint8 array is taken as the bytes the kernels compare with, anything else as floats in [0, 1] through
+    confidence_threshold.  A wrong length or a value out of range: ValueError."""
+    class_num = int(class_num)
+    if not 1 <= class_num <= 256:
+        raise ValueError("class_num must be in 1..256, got %r" % (class_num,))
+    if isinstance(thresholds, torch.Tensor):
+        thresholds = thresholds.detach().cpu().numpy()
+    a = np.asarray(thresholds)
+    if a.ndim > 1 or a.dtype == object or a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+        raise ValueError("class_thresholds: one value or %d values, floats in [0, 1] or a uint8 array of bytes" % class_num)
+    if a.ndim == 1 and a.shape[0] != class_num:
+        raise ValueError("class_thresholds: %d values for %d classes" % (a.shape[0], class_num))
+    if a.dtype == np.uint8:
+        values = a.astype(np.uint8)
+    else:
+        try:
+            values = np.array([confidence_threshold(v) for v in a.reshape(-1)], dtype=np.uint8)
+        except ValueError:
+            raise ValueError("class_thresholds: every value must be in [0, 1] (bytes go in a uint8 array), got %r" % (thresholds,))
+    table = np.zeros(256, dtype=np.uint8)
+    table[:class_num] = values if a.ndim == 1 else values.reshape(())
+    return table
+
+
+def class_threshold_table(thresholds, class_num, device):
+    """The 256-byte device table the _pc launches read (class_threshold_bytes on the device)."""
+    return torch.from_numpy(class_threshold_bytes(thresholds, class_num)).to(device)
+
+
+def _threshold_args(min_confidence, class_thresholds, device):
+    """(entry-point suffix, threshold argument) of a confidence launch: the scalar byte, or the device table with the _pc symbol"""
+    if class_thresholds is None:
+        return "", confidence_threshold(min_confidence)
+    if confidence_threshold(min_confidence) != 0:
+        raise ValueError("class_thresholds and min_confidence exclude each other (got min_confidence=%r)" % (min_confidence,))
+    t = class_thresholds
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.numel() == 256 and t.is_contiguous() and t.device == device):
+        raise ValueError("class_thresholds must be the uint8[256] tensor of class_threshold_table on %s" % (device,))
+    return "_pc", _p(t)
+
+
+def bilinear_argmax_conf(x, size, min_confidence=0.0, ignore_label=255, classes=None, conf=None, class_thresholds=None):
     """fs_bilinear_argmax_conf: NHWC logits view (N, C, h, w) -> (classes, conf), both uint8 (N, Ho, Wo): the arg-max of the up-sample with
     `ignore_label` where the confidence byte is below confidence_threshold(min_confidence), and the byte q = floor(255 p + 0.5) of the
-    winner's softmax probability.  classes=False / conf=False: that map is not written (None is returned in its place)."""
+    winner's softmax probability.  classes=False / conf=False: that map is not written (None is returned in its place).
+    class_thresholds (a class_threshold_table): fs_bilinear_argmax_conf_pc, class k is kept where q >= table[k]."""
     d = _logits_resize_desc(x, size)
-    mc, ig = confidence_threshold(min_confidence), _check_ignore_label(ignore_label)
+    ig = _check_ignore_label(ignore_label)
+    pc, th = _threshold_args(min_confidence, class_thresholds, x.device)
     shape = (d.N, d.Ho, d.Wo)
     classes = None if classes is False else _u8_map(classes, shape, x.device, "classes")
     conf = None if conf is False else _u8_map(conf, shape, x.device, "conf")
-    call("fs_bilinear_argmax_conf", _stream(), ctypes.byref(d), _p(x), _p(classes), _p(conf), mc, ig)
+    call("fs_bilinear_argmax_conf" + pc, _stream(), ctypes.byref(d), _p(x), _p(classes), _p(conf), th, ig)
     return classes, conf
 
 
-def score_confidence(score, C, min_confidence=0.0, ignore_label=255, classes=None, conf=None):
+def score_confidence(score, C, min_confidence=0.0, ignore_label=255, classes=None, conf=None, class_thresholds=None):
     """fs_score_confidence on a contiguous fp32 score buffer (..., cs) of summed exp-scores: per pixel the first maximum over the first C
-    channels and its share of their sum as a byte -> (classes, conf), uint8 of shape score.shape[:-1].  classes=False / conf=False as in
-    bilinear_argmax_conf."""
+    channels and its share of their sum as a byte -> (classes, conf), uint8 of shape score.shape[:-1].  classes=False / conf=False and
+    class_thresholds (fs_score_confidence_pc) as in bilinear_argmax_conf."""
     assert score.dtype == torch.float32 and score.is_contiguous() and score.dim() >= 2
-    mc, ig = confidence_threshold(min_confidence), _check_ignore_label(ignore_label)
+    ig = _check_ignore_label(ignore_label)
+    pc, th = _threshold_args(min_confidence, class_thresholds, score.device)
     shape = tuple(score.shape[:-1])
     classes = None if classes is False else _u8_map(classes, shape, score.device, "classes")
     conf = None if conf is False else _u8_map(conf, shape, score.device, "conf")
-    call("fs_score_confidence", _stream(), _p(score), score.numel() // score.shape[-1], int(score.shape[-1]), int(C), _p(classes), _p(conf), mc, ig)
+    call("fs_score_confidence" + pc, _stream(), _p(score), score.numel() // score.shape[-1], int(score.shape[-1]), int(C), _p(classes), _p(conf),
+         th, ig)
     return classes, conf
+
+
+def confidence_hist(classes, conf, C, gt=None, hist=None):
+    """fs_confidence_hist: adds the (class, confidence byte) counts of two uint8 maps of one shape into `hist`, an int64 (2, C, 256) device
+    tensor (created zeroed when None) and returns it.  Plane 0 alone without labels; with gt (uint8 / int32 / int64, the maps' shape):
+    plane 0 where the class is the label, plane 1 where it is not, pixels labelled outside [0, C) skipped.  The maps may be views at any
+    byte offset as long as they are contiguous."""
+    assert classes.dtype == torch.uint8 and conf.dtype == torch.uint8 and classes.is_contiguous() and conf.is_contiguous()
+    assert classes.shape == conf.shape, (classes.shape, conf.shape)
+    if hist is None:
+        hist = torch.zeros((2, int(C), 256), dtype=torch.int64, device=classes.device)
+    assert hist.dtype == torch.int64 and hist.is_contiguous() and tuple(hist.shape) == (2, int(C), 256), "hist: a contiguous int64 (2, C, 256)"
+    gt_bytes = 0
+    if gt is not None:
+        assert gt.shape == classes.shape and gt.is_contiguous(), "labels: the maps' shape, contiguous"
+        try:
+            gt_bytes = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}[gt.dtype]
+        except KeyError:
+            raise TypeError("labels must be uint8, int32 or int64, got %s" % gt.dtype)
+    call("fs_confidence_hist", _stream(), _p(classes), _p(conf), _p(gt), gt_bytes, classes.numel(), int(C), _p(hist))
+    return hist
 
 
 def bilinear_bwd(dy, y_out, in_shape, relu, dtype, out_nchw=0, dx_cs=None):

@@ -586,6 +586,27 @@ fs_status fs_bilinear_argmax_conf(void* stream, const fs_resize_desc* d, const v
  * conf = max / sum over c < C; a sum that is zero or not finite gives q = 0. */
 fs_status fs_score_confidence(void* stream, const float* score, long long pixels, int cs, int C, unsigned char* classes,
                               unsigned char* conf, int min_conf, int ignore_label);
+/* Per-class thresholds (class-balanced pseudo-labels).  Three added symbols: no struct and no existing signature changed, so
+ * FS_ABI_VERSION stays 221, as for the two confidence symbols above; a library built before them simply does not export them.
+ *
+ * The _pc forms are fs_bilinear_argmax_conf / fs_score_confidence in everything - arguments, refusals, the x8 strip and the generic
+ * path, the up-sample, the arg-max, the operation order of the confidence and the `conf` bytes - except the decision: a pixel with
+ * arg-max class k and byte q is KEPT iff q >= min_conf_by_class[k].  min_conf_by_class is a DEVICE pointer to 256 readable bytes, entry
+ * k for class k; entries >= C are never consulted; NULL is FS_ERR_INVALID.  The table is read when the kernel runs, so a captured
+ * launch follows later writes to it that are ordered on its stream.  With all entries equal to m the class map is bit for bit the
+ * scalar form's with min_conf = m. */
+fs_status fs_bilinear_argmax_conf_pc(void* stream, const fs_resize_desc* d, const void* x, unsigned char* classes, unsigned char* conf,
+                                     const unsigned char* min_conf_by_class, int ignore_label);
+fs_status fs_score_confidence_pc(void* stream, const float* score, long long pixels, int cs, int C, unsigned char* classes,
+                                 unsigned char* conf, const unsigned char* min_conf_by_class, int ignore_label);
+/* What such thresholds are chosen from: hist is uint64 [2][C][256], zeroed by the caller once per run.  Pixel i with k = classes[i],
+ * q = conf[i]: skipped if k >= C (a masked pixel carries its ignore_label).  gt == NULL: hist[0][k][q] += 1 and plane 1 is not touched
+ * at all.  gt given (uint8 / int32 / int64 by gt_bytes = 1 / 4 / 8, naturally aligned): skipped if gt[i] is outside [0, C), else
+ * hist[0][k][q] += 1 where k == gt[i] (right) and hist[1][k][q] += 1 where k != gt[i] (wrong).  C in 1..32 (above: FS_ERR_UNSUPPORTED -
+ * two planes of 32 x 256 uint32 counters are a block's 64 KB of LDS); n >= 0, n == 0 launches nothing; classes and conf may start at
+ * any byte.  Integer atomics only: exact and independent of arrival order. */
+fs_status fs_confidence_hist(void* stream, const unsigned char* classes, const unsigned char* conf, const void* gt, int gt_bytes,
+                             long long n, int C, unsigned long long* hist);
 /* hist_info of tools/seg_opr/metric.py:7-17 on the device: over the n pixels with 0 <= gt < n_cl,
  * hist[n_cl * gt + pred] += 1, counts[0] += 1 (labeled), counts[1] += (pred == gt) (correct).  gt is uint8 / int32 / int64
  * (gt_bytes = 1 / 4 / 8; 255 or -1 = ignore); hist (n_cl * n_cl) and counts (2) are uint64 accumulators the caller zeroes
