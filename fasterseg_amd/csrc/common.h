@@ -199,7 +199,7 @@ __device__ __forceinline__ uint32_t pack2_f16(float lo, float hi) {          // 
     v[1] = (_Float16)f16_clamp(hi);
     return __builtin_bit_cast(uint32_t, v);
 }
-// four consecutive fp16 channels (one 8-byte load): the logits readers' quad (resize.hip, eval.hip, eval_ms.hip)
+// four consecutive fp16 channels (one 8-byte load): the fp16 form of logits_up.h's quad loader
 __device__ __forceinline__ void f16_load4(const f16_t* p, float* o) {
     typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
     const f16x4 v = __builtin_bit_cast(f16x4, *reinterpret_cast<const uint2*>(p));

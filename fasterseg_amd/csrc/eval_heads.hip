@@ -4,8 +4,8 @@
 // = 0..4), and every image of every sweep pays exp() of the up-sampled (19, H, W) score map, its copy to the host, np.argmax and
 // hist_info there (tools/engine/evaluator.py:297-318 val_func_process, tools/seg_opr/metric.py:7-17 hist_info).  The five heads
 // come out of one forward (model_search.py _tail), so here one forward feeds one launch that, per output pixel and per head,
-//   - evaluates the align_corners=True bilinear up-sample of the head's low-resolution NHWC logits (the tap arithmetic and the
-//     expression of bilinear_argmax_kernel / bilinear_argmax8_kernel in eval.hip, which are resize.hip's),
+//   - evaluates the align_corners=True bilinear up-sample of the head's low-resolution NHWC logits (logits_up.h: the class values
+//     of eval.hip's kernels, under the bit contract stated there),
 //   - takes the arg-max over the C classes (strict >: the first maximum wins, as np.argmax),
 //   - counts the pixel into the head's hist[k][C * gt + pred] and counts[k] = {labeled, correct} when 0 <= gt < C
 //     (255 / -1 / >= C: ignored), which is what fs_bilinear_argmax + fs_hist_info compute head by head.
@@ -14,7 +14,7 @@
 // bit-exact and reproducible.
 #include <algorithm>
 
-#include "common.h"
+#include "logits_up.h"
 
 namespace fs {
 
@@ -41,21 +41,6 @@ __device__ __forceinline__ int head_cs(const HeadsArgs& a, int k) {
     return r;
 }
 
-template <typename T> struct HQuad;
-template <> struct HQuad<float> {
-    static __device__ __forceinline__ void load(const float* p, float* o) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p);
-        o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
-    }
-};
-template <> struct HQuad<bf16_t> {
-    static __device__ __forceinline__ void load(const bf16_t* p, float* o) {
-        const uint2 v = *reinterpret_cast<const uint2*>(p);
-        o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
-        o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
-    }
-};
-
 // the label of pixel i as a class index, -1 when it is not counted (255, -1, >= C); gt_bytes is uniform
 __device__ __forceinline__ int label_at(const void* gt, int gt_bytes, long long i, int C) {
     long long g;
@@ -63,21 +48,6 @@ __device__ __forceinline__ int label_at(const void* gt, int gt_bytes, long long 
     else if (gt_bytes == 4) g = (long long)static_cast<const int*>(gt)[i];
     else g = static_cast<const long long*>(gt)[i];
     return (g >= 0 && g < C) ? (int)g : -1;
-}
-
-__device__ __forceinline__ void zero_lds(unsigned int* local, int n) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) local[i] = 0;
-    __syncthreads();
-}
-
-// head k's local[j]: j < C * C -> hist[k * C * C + j], j = C * C -> counts[2k] (labeled), C * C + 1 -> counts[2k + 1] (correct)
-__device__ __forceinline__ void flush_lds(const unsigned int* local, int k, int C, unsigned long long* hist, unsigned long long* counts) {
-    __syncthreads();
-    const int bins = C * C;
-    for (int j = threadIdx.x; j < bins + 2; j += blockDim.x) {
-        const unsigned int v = local[j];
-        if (v) atomicAdd(j < bins ? hist + (long long)k * bins + j : counts + 2 * k + (j - bins), (unsigned long long)v);
-    }
 }
 
 // x8 case (the heads' own up-sample, model_search.py _tail): one lane = one 1 x 8 output strip of one row of head blockIdx.y; the 8
@@ -90,7 +60,7 @@ __global__ __launch_bounds__(256) void heads_confusion8_kernel(HeadsArgs a, int 
                                                                unsigned long long* __restrict__ hist, unsigned long long* __restrict__ counts) {
     extern __shared__ __attribute__((aligned(16))) unsigned int local[];
     const int k = blockIdx.y;
-    zero_lds(local, C * C + 2);
+    lds_zero(local, C * C + 2);
     const T* x = static_cast<const T*>(head_ptr(a, k));
     const int cs = head_cs(a, k);
     const int w8 = Wo >> 3;
@@ -111,34 +81,18 @@ __global__ __launch_bounds__(256) void heads_confusion8_kernel(HeadsArgs a, int 
         }
         if (nlab == 0) continue;                            // no counted pixel in the strip: nothing to evaluate
         labeled += nlab;
-        const Tap th = make_tap(rh, oh, Hi);
-        const int bx = make_tap(rw, ow0, Wi).i0;
-        const T* r0 = x + ((long long)n * Hi + th.i0) * Wi * cs;
-        const T* r1 = x + ((long long)n * Hi + th.i1) * Wi * cs;
+        Tap th;
+        int bx;
         float top[3][CQ * 4], bot[3][CQ * 4];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int col = min(bx + j, Wi - 1);
-#pragma unroll
-            for (int q = 0; q < CQ; ++q) {
-                HQuad<T>::load(r0 + (long long)col * cs + q * 4, &top[j][q * 4]);
-                HQuad<T>::load(r1 + (long long)col * cs + q * 4, &bot[j][q * 4]);
-            }
-        }
+        strip_stage<T, CQ>(x, cs, n, oh, ow0, Hi, Wi, rh, rw, th, bx, top, bot);
 #pragma unroll
         for (int dx = 0; dx < 8; ++dx) {
-            const Tap tw = make_tap(rw, ow0 + dx, Wi);
-            const bool a1 = (tw.i0 - bx) >= 1;              // left tap is source column bx + 1 (else bx)
-            const int rel1 = tw.i1 - bx;                    // right tap: bx, bx + 1 or bx + 2
+            const StripCol s = strip_col(rw, ow0 + dx, Wi, bx);
             float best = -INFINITY;
             int arg = 0;
 #pragma unroll
             for (int c = 0; c < CQ * 4; ++c) {
-                const float p00 = a1 ? top[1][c] : top[0][c];
-                const float p10 = a1 ? bot[1][c] : bot[0][c];
-                const float p01 = rel1 >= 2 ? top[2][c] : (rel1 == 1 ? top[1][c] : top[0][c]);
-                const float p11 = rel1 >= 2 ? bot[2][c] : (rel1 == 1 ? bot[1][c] : bot[0][c]);
-                const float val = bilerp(th, tw, p00, p01, p10, p11);
+                const float val = strip_value<CQ>(top, bot, th, s, c);
                 if (c < C && val > best) {
                     best = val;
                     arg = c;
@@ -152,7 +106,8 @@ __global__ __launch_bounds__(256) void heads_confusion8_kernel(HeadsArgs a, int 
     }
     if (labeled) atomicAdd(&local[C * C], labeled);
     if (correct) atomicAdd(&local[C * C + 1], correct);
-    flush_lds(local, k, C, hist, counts);
+    // local[j]: j < C * C -> hist[k * C * C + j], j = C * C -> counts[2k] (labeled), C * C + 1 -> counts[2k + 1] (correct)
+    lds_flush(local, C * C, hist + (long long)k * (C * C), 2, counts + 2 * k);
 }
 
 // any other geometry: one lane = one output pixel of head blockIdx.y, the classes 4 at a time
@@ -162,7 +117,7 @@ __global__ __launch_bounds__(256) void heads_confusion_kernel(HeadsArgs a, int N
                                                               unsigned long long* __restrict__ hist, unsigned long long* __restrict__ counts) {
     extern __shared__ __attribute__((aligned(16))) unsigned int local[];
     const int k = blockIdx.y;
-    zero_lds(local, C * C + 2);
+    lds_zero(local, C * C + 2);
     const T* x = static_cast<const T*>(head_ptr(a, k));
     const int cs = head_cs(a, k);
     const long long total = (long long)N * Ho * Wo;
@@ -181,14 +136,11 @@ __global__ __launch_bounds__(256) void heads_confusion_kernel(HeadsArgs a, int N
         float best = -INFINITY;
         int arg = 0;
         for (int c0 = 0; c0 < C; c0 += 4) {
-            float p00[4], p01[4], p10[4], p11[4];
-            HQuad<T>::load(r0 + (long long)tw.i0 * cs + c0, p00);
-            HQuad<T>::load(r0 + (long long)tw.i1 * cs + c0, p01);
-            HQuad<T>::load(r1 + (long long)tw.i0 * cs + c0, p10);
-            HQuad<T>::load(r1 + (long long)tw.i1 * cs + c0, p11);
+            float p[4][4];
+            quad_stage(r0, r1, cs, tw, c0, p);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float v = bilerp(th, tw, p00[j], p01[j], p10[j], p11[j]);
+                const float v = quad_value(p, th, tw, j);
                 if (c0 + j < C && v > best) {
                     best = v;
                     arg = c0 + j;
@@ -201,7 +153,8 @@ __global__ __launch_bounds__(256) void heads_confusion_kernel(HeadsArgs a, int N
     }
     if (labeled) atomicAdd(&local[C * C], labeled);
     if (correct) atomicAdd(&local[C * C + 1], correct);
-    flush_lds(local, k, C, hist, counts);
+    // local[j]: j < C * C -> hist[k * C * C + j], j = C * C -> counts[2k] (labeled), C * C + 1 -> counts[2k + 1] (correct)
+    lds_flush(local, C * C, hist + (long long)k * (C * C), 2, counts + 2 * k);
 }
 
 template <typename T>

@@ -13,32 +13,17 @@
 //                               total, and on the last scale the uint8 arg-max of the updated total.
 // No float atomics: the windows of a scale are issued one after another on one stream, so every canvas pixel is a plain
 // read-modify-write and the result is bitwise reproducible.
-#include "common.h"
+#include "logits_up.h"
 
 namespace fs {
 
 namespace {
 
-template <typename T> struct LoadQuad;
-template <> struct LoadQuad<float> {
-    static __device__ __forceinline__ f32x4 load(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-};
-template <> struct LoadQuad<bf16_t> {
-    static __device__ __forceinline__ f32x4 load(const bf16_t* p) {
-        const uint2 v = *reinterpret_cast<const uint2*>(p);
-        f32x4 o;
-        o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
-        o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
-        return o;
-    }
-};
-template <> struct LoadQuad<f16_t> {
-    static __device__ __forceinline__ f32x4 load(const f16_t* p) {
-        f32x4 o;
+template <typename T> struct LoadQuad {                // logits_up.h's quad as an f32x4
+    static __device__ __forceinline__ f32x4 load(const T* p) {
         float t[4];
-        f16_load4(p, t);
-        o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = t[3];
-        return o;
+        Quad<T>::load(p, t);
+        return f32x4{t[0], t[1], t[2], t[3]};
     }
 };
 

@@ -17,26 +17,11 @@
 //              four cells.  The first version gathered per low-resolution pixel and re-evaluated every full-resolution pixel
 //              four times inside divergent loops: 565 us (OHEM, mean of the three heads) / 1057 us (KL) per launch on the
 //              student step's heads; now 491 / 528 / 184 us (x8 / x16 / x32 OHEM) and 592 us (KL), still latency-bound.
-#include "common.h"
+#include "logits_up.h"       // Quad<T>::load only
 
 namespace fs {
 
 constexpr int LU_MAXC = 20;                 // classes held in registers (19 for Cityscapes), padded to whole quads
-
-template <typename T> struct QuadL;
-template <> struct QuadL<float> {
-    static __device__ __forceinline__ void load(const float* p, float* o) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p);
-        o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
-    }
-};
-template <> struct QuadL<bf16_t> {
-    static __device__ __forceinline__ void load(const bf16_t* p, float* o) {
-        const uint2 v = *reinterpret_cast<const uint2*>(p);
-        o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
-        o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
-    }
-};
 
 struct UpGeom {
     int N, h, w, H, W, C, cs;
@@ -67,10 +52,10 @@ __device__ __forceinline__ void interp_logits(const T* __restrict__ lo, const Up
     for (int q = 0; q < LU_MAXC / 4; ++q) {
         if (q * 4 < g.C) {
             float p00[4], p01[4], p10[4], p11[4];
-            QuadL<T>::load(r0 + (long long)tw.i0 * g.cs + q * 4, p00);
-            QuadL<T>::load(r0 + (long long)tw.i1 * g.cs + q * 4, p01);
-            QuadL<T>::load(r1 + (long long)tw.i0 * g.cs + q * 4, p10);
-            QuadL<T>::load(r1 + (long long)tw.i1 * g.cs + q * 4, p11);
+            Quad<T>::load(r0 + (long long)tw.i0 * g.cs + q * 4, p00);
+            Quad<T>::load(r0 + (long long)tw.i1 * g.cs + q * 4, p01);
+            Quad<T>::load(r1 + (long long)tw.i0 * g.cs + q * 4, p10);
+            Quad<T>::load(r1 + (long long)tw.i1 * g.cs + q * 4, p11);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 out[q * 4 + k] = bilerp(th, tw, p00[k], p01[k], p10[k], p11[k]);
@@ -148,10 +133,10 @@ __device__ __forceinline__ void cell_sweep(float (&S)[16], float sign, int c0, c
         const int i1 = i + (i < g.h - 1 ? 1 : 0), j1 = j + (j < g.w - 1 ? 1 : 0);
         const T* r0 = lo + ((long long)n * g.h + i) * g.w * g.cs + c0;
         const T* r1 = lo + ((long long)n * g.h + i1) * g.w * g.cs + c0;
-        QuadL<T>::load(r0 + (long long)j * g.cs, L[0]);
-        QuadL<T>::load(r0 + (long long)j1 * g.cs, L[1]);
-        QuadL<T>::load(r1 + (long long)j * g.cs, L[2]);
-        QuadL<T>::load(r1 + (long long)j1 * g.cs, L[3]);
+        Quad<T>::load(r0 + (long long)j * g.cs, L[0]);
+        Quad<T>::load(r0 + (long long)j1 * g.cs, L[1]);
+        Quad<T>::load(r1 + (long long)j * g.cs, L[2]);
+        Quad<T>::load(r1 + (long long)j1 * g.cs, L[3]);
     }
     const int count = ny * nx;
     for (int k = first; k < count; k += step) {
@@ -180,10 +165,10 @@ __device__ __forceinline__ void cell_sweep(float (&S)[16], float sign, int c0, c
             const T* r0 = lo + ((long long)n * gl.h + uh.i0) * gl.w * gl.cs + c0;
             const T* r1 = lo + ((long long)n * gl.h + uh.i1) * gl.w * gl.cs + c0;
             float p00[4], p01[4], p10[4], p11[4];
-            QuadL<T>::load(r0 + (long long)uw.i0 * gl.cs, p00);
-            QuadL<T>::load(r0 + (long long)uw.i1 * gl.cs, p01);
-            QuadL<T>::load(r1 + (long long)uw.i0 * gl.cs, p10);
-            QuadL<T>::load(r1 + (long long)uw.i1 * gl.cs, p11);
+            Quad<T>::load(r0 + (long long)uw.i0 * gl.cs, p00);
+            Quad<T>::load(r0 + (long long)uw.i1 * gl.cs, p01);
+            Quad<T>::load(r1 + (long long)uw.i0 * gl.cs, p10);
+            Quad<T>::load(r1 + (long long)uw.i1 * gl.cs, p11);
 #pragma unroll
             for (int c = 0; c < 4; ++c) v[c] = bilerp(uh, uw, p00[c], p01[c], p10[c], p11[c]);
         }

@@ -8,7 +8,7 @@
 // operations.py:275-276), the store into a channel slice of a wider buffer (torch.cat, model_seg.py:307), and
 // the final logits written straight to a contiguous NCHW tensor (model_seg.py:365).
 // The backward is a gather over the output pixels that touch each input pixel: no atomics, deterministic.
-#include "common.h"
+#include "logits_up.h"
 #include "group.h"
 
 namespace fs {
@@ -68,24 +68,7 @@ __device__ __forceinline__ Tap make_tap_rn(float scale, int dst, int in_size) {
 
 // NHWC (channel stride padded to a multiple of 4, pad lanes readable) -> NCHW.  One lane: 4 consecutive ow x 4 channels.
 // Each tap is ONE vector load of 4 channels (8 B bf16 / 16 B fp32); the low-resolution logits are L2-resident, the
-// kernel is bound by the NCHW write (16-byte stores per channel plane).
-template <typename T> struct Quad;     // 4 consecutive channels
-template <> struct Quad<float> {
-    static __device__ __forceinline__ void load(const float* p, float* o) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p);
-        o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
-    }
-};
-template <> struct Quad<bf16_t> {
-    static __device__ __forceinline__ void load(const bf16_t* p, float* o) {
-        const uint2 v = *reinterpret_cast<const uint2*>(p);
-        o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
-        o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
-    }
-};
-template <> struct Quad<f16_t> {
-    static __device__ __forceinline__ void load(const f16_t* p, float* o) { f16_load4(p, o); }
-};
+// kernel is bound by the NCHW write (16-byte stores per channel plane).  Quad<T>::load (logits_up.h): 4 consecutive channels.
 template <typename TO> __device__ __forceinline__ void store4(TO* dst, const float* v);
 template <> __device__ __forceinline__ void store4<float>(float* dst, const float* v) {
     // the logits are written once and not read again by this graph: stream them past the caches
