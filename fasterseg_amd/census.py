@@ -18,6 +18,7 @@ import torch
 from . import _lib
 from . import kernels as K
 from ._lib import FS_CONV_TRANSPOSED, CensusEntry, ConvDesc, KernelTime, call
+from .devtime import captured_ms
 
 IGEMM, HALO, WGRAD, STATS = 0, 1, 2, 0x100
 FAMILY_NAMES = {IGEMM: "conv_igemm (fwd + dgrad)", HALO: "conv3x3_halo", WGRAD: "conv_wgrad"}
@@ -94,31 +95,6 @@ def conv_bytes(d):
     return es * (in_px * d.Cin + d.Cout * d.R * d.S * d.Cin + d.N * d.Ho * d.Wo * d.Cout)
 
 
-def _graph_time_ms(fn, reps=20, rounds=3):
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        fn(ctypes.c_void_p(side.cuda_stream))
-        side.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            for _ in range(reps):
-                fn(st)
-        g.replay()
-        best = None
-        for _ in range(rounds):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            g.replay()
-            e1.record()
-            e1.synchronize()
-            t = e0.elapsed_time(e1) / reps
-            best = t if best is None or t < best else best
-    torch.cuda.current_stream().wait_stream(side)
-    return best
-
-
 def time_entry(family, d, device="cuda"):
     """Device time (ms) of one launch of this geometry on random operands."""
     dt = {_lib.FS_F32: torch.float32, _lib.FS_BF16: torch.bfloat16, _lib.FS_F16: torch.float16}[d.dtype]
@@ -133,18 +109,18 @@ def time_entry(family, d, device="cuda"):
         dy = torch.randn(d.N * d.Ho * d.Wo * d.y_cs, device=device).to(dt)
         dw = torch.zeros(d.Cout * d.R * d.S * d.Cin, dtype=torch.float32, device=device)        # [O][R][S][I]
         o_s, i_s, t_s = d.R * d.S * d.Cin, 1, d.Cin
-        return _graph_time_ms(lambda st: call("fs_conv2d_wgrad_strided", st, ctypes.byref(dd), K._p(x), K._p(dy), K._p(dw), o_s, i_s, t_s))
+        return captured_ms(lambda st: call("fs_conv2d_wgrad_strided", st, ctypes.byref(dd), K._p(x), K._p(dy), K._p(dw), o_s, i_s, t_s))
     if fam == HALO:
         n = _lib.lib().fs_packed_weight_frag_elems(d.Cout, d.Cin, d.dtype)
         w = (torch.randn(n, device=device) * 0.05).to(dt)
-        return _graph_time_ms(lambda st: call("fs_conv3x3_s1_fwd", st, ctypes.byref(dd), K._p(x), K._p(w), None, None, K._p(y), K._p(stats)))
+        return captured_ms(lambda st: call("fs_conv3x3_s1_fwd", st, ctypes.byref(dd), K._p(x), K._p(w), None, None, K._p(y), K._p(stats)))
     rows = max(d.w_os, d.R * d.S * max(d.w_ts, d.Cin)) if d.w_os else d.R * d.S * d.Cin
     # two-segment descriptors (fused pairs) read filter rows n_jump further / k_jump elements further: size the bank for them
     n_rows = d.Cout + (max(d.n_jump, 0) if d.n_seg > 0 else 0)
     w = (torch.randn(n_rows * rows + (abs(d.k_jump) if d.k_seg > 0 else 0), device=device) * 0.05).to(dt)
     ws = torch.empty(K.WORKSPACE_BYTES, dtype=torch.uint8, device=device)
-    return _graph_time_ms(lambda st: call("fs_conv2d_fwd_ws", st, ctypes.byref(dd), K._p(x), K._p(w), None, None, K._p(y), K._p(stats),
-                                          K._p(ws), K.WORKSPACE_BYTES))
+    return captured_ms(lambda st: call("fs_conv2d_fwd_ws", st, ctypes.byref(dd), K._p(x), K._p(w), None, None, K._p(y), K._p(stats),
+                                       K._p(ws), K.WORKSPACE_BYTES))
 
 
 def roofline(entries, dtype_name, peak_tflops, peak_hbm_gbs=8000.0, max_shapes=160, coverage=0.95):

@@ -1411,30 +1411,16 @@ class InferenceEngine:
         two events (median of `rounds`), so the figure is kernel duration + one dependent-kernel boundary (~1.5 us) and
         is free of Python launch overhead; rocprofv3 --kernel-trace durations of the same kernels (profiles/) are the
         cross-check.  Returns [dict(label, family, ms, flops, bytes)] in plan order."""
-        out = []
+        from . import devtime
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            st = ctypes.c_void_p(side.cuda_stream)
-            self._launch_all_on(st)
+            self._launch_all_on(ctypes.c_void_p(side.cuda_stream))          # the whole plan warms once, then every launch on this stream
             side.synchronize()
-            for c in self.calls:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=side):
-                    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-                    for _ in range(repeats):
-                        call(c["fn"], st, *c["args"])
-                g.replay()
-                times = []
-                for _ in range(rounds):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    g.replay()
-                    e1.record()
-                    e1.synchronize()
-                    times.append(e0.elapsed_time(e1) / repeats)
-                times.sort()
-                out.append(dict(label=c["label"], family=c["family"], ms=times[len(times) // 2], flops=c["flops"], bytes=c["bytes"]))
+        out = []
+        for c in self.calls:
+            ms = devtime.captured_ms(lambda st: call(c["fn"], st, *c["args"]), repeats, rounds, pick=lambda t: sorted(t)[len(t) // 2], stream=side, warm=False)
+            out.append(dict(label=c["label"], family=c["family"], ms=ms, flops=c["flops"], bytes=c["bytes"]))
         torch.cuda.current_stream().wait_stream(side)
         return out
 

@@ -8,15 +8,7 @@ dispatch time; `graph=False` times eager launches like the reference's PyTorch f
 """
 import torch
 
-
-def _time_ms(fn, iters):
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    stop.record()
-    stop.synchronize()
-    return start.elapsed_time(stop)
+from .devtime import block_ms
 
 
 def compute_latency_ms_hip(model, input_size, iterations=None, device=None, graph=True, min_calib_ms=200.0, budget_ms=600.0):
@@ -53,15 +45,14 @@ def compute_latency_ms_hip(model, input_size, iterations=None, device=None, grap
             run()
         torch.cuda.synchronize()
         if iterations is None:     # calibrate like darts_utils.py:144-154 (grow until the trial is long enough)
-            iterations, elapsed = 20, 0.0
+            iterations = 20
             while True:
-                elapsed = _time_ms(run, iterations)
-                if elapsed >= min_calib_ms or iterations >= (1 << 16):
+                per = block_ms(run, iterations, sync=False)
+                if per * iterations >= min_calib_ms or iterations >= (1 << 16):
                     break
                 iterations *= 2
-            per = elapsed / iterations
             iterations = max(10, int(budget_ms / max(per, 1e-4)))
-        latency = _time_ms(run, iterations) / iterations
+        latency = block_ms(run, iterations, sync=False)
     model.train(was_training)
     return latency
 

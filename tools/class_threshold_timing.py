@@ -28,28 +28,11 @@ if ROOT not in sys.path:
 C = 19
 
 
-def block_ms(step, n):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        step()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / n
+from fasterseg_amd.devtime import block_ms, capture  # noqa: E402
 
 
 def captured(fn, launches):
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        fn()
-        side.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            for _ in range(launches):
-                fn()
-    torch.cuda.current_stream().wait_stream(side)
+    g = capture(lambda st: fn(), launches)         # the kernels wrappers launch on the current stream: the capturing one
     torch.cuda.synchronize()
     return g
 

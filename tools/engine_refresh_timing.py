@@ -22,19 +22,6 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def frame_ms(eng, frames):
-    for _ in range(20):
-        eng.run()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(frames):
-        eng.run()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / frames
-
-
 def host_ms(fn, calls, warmup):
     for _ in range(warmup):
         fn()
@@ -58,6 +45,7 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X"
     from fasterseg_amd import archs, census
+    from fasterseg_amd.devtime import block_ms
     from fasterseg_amd.engine import InferenceEngine
     shape = tuple(args.shape)
     nets = [archs.init_weight(archs.build_derived(1, training=False, lasts=[2, 1]), seed).cuda().eval() for seed in (12345, 999)]
@@ -81,7 +69,7 @@ def main():
     eng.input.copy_(x)
 
     # (c) frame time before the reload
-    row["frame_ms_before"] = round(frame_ms(eng, args.frames), 4)
+    row["frame_ms_before"] = round(block_ms(eng.run, args.frames, warm=20), 4)
 
     # (b) reload
     t0 = time.perf_counter()
@@ -109,7 +97,7 @@ def main():
                refresh_kernel_us=round(kernel_ms * 1e3, 2), refresh_GB_per_s=round(tab["bytes"] / 1e9 / (kernel_ms / 1e3), 1) if kernel_ms else None)
 
     # (c) frame time after the reload
-    row["frame_ms_after"] = round(frame_ms(eng, args.frames), 4)
+    row["frame_ms_after"] = round(block_ms(eng.run, args.frames, warm=20), 4)
     line = json.dumps(row)
     print(line)
     if args.out:

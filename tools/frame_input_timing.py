@@ -24,18 +24,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from fasterseg_amd.devtime import block_ms  # noqa: E402
+
 MEAN, STD = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
-
-
-def block_ms(step, frames):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(frames):
-        step()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / frames
 
 
 def main():

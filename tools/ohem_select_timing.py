@@ -46,19 +46,6 @@ def torch_chain(true_prob, nll, tgt, thresh, min_kept):
     return loss, kept.to(torch.uint8), count, threshold
 
 
-def timed(fn, calls, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pixels", type=int, default=12 * 512 * 1024)
@@ -69,6 +56,7 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X"
     from fasterseg_amd import _lib, census
+    from fasterseg_amd.devtime import block_ms
     from fasterseg_amd.losses import ohem_select
     P = args.pixels
     thresh, min_kept = 0.7, P // 16
@@ -84,8 +72,8 @@ def main():
     assert abs(float(result[0]) - float(loss)) <= 1e-5 * abs(float(loss)), (float(result[0]), float(loss))
     sel_ms, chain_ms = [], []
     for _ in range(args.rounds):
-        sel_ms.append(timed(select, args.calls, args.warmup))
-        chain_ms.append(timed(chain, args.calls, args.warmup))
+        sel_ms.append(block_ms(select, args.calls, warm=args.warmup))
+        chain_ms.append(block_ms(chain, args.calls, warm=args.warmup))
     with census.recording(level=2) as rec:
         select()
     kernels = {k: {"launches": v[0], "us": round(v[1] * 1e3, 2), "bytes": rec.kernel_bytes.get(k, 0.0)}

@@ -37,6 +37,7 @@ def tables():
 def launches(spec, n, warmup):
     from fasterseg_amd import kernels as K
     from fasterseg_amd import visualize as V
+    from fasterseg_amd.devtime import block_ms
     rs = np.random.RandomState(2)
     img = torch.from_numpy(rs.randint(0, 256, size=(H, W, 3)).astype(np.uint8)).cuda()
     pred = torch.from_numpy(np.kron(rs.randint(0, 19, size=(H // 32, W // 32)), np.ones((32, 32))).astype(np.uint8)).cuda()
@@ -55,16 +56,7 @@ def launches(spec, n, warmup):
     }
     rows = []
     for name, (fn, nbytes) in cases.items():
-        for _ in range(warmup):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        e1.synchronize()
-        ms = e0.elapsed_time(e1) / n
+        ms = block_ms(fn, n, warm=warmup)
         rows.append({"case": name, "shape": [H, W], "launches": n, "ms_per_launch": round(ms, 4), "MB": round(nbytes / 1e6, 2),
                      "GB_per_s": round(nbytes / 1e9 / (ms / 1e3), 1)})
     return rows

@@ -37,6 +37,7 @@ class Cfg:
 def measure(name, resident, images, labels, batches, warmup):
     from fasterseg_amd import census as C
     from fasterseg_amd.dataloader import ArraySource, DeviceTrainLoader
+    from fasterseg_amd.devtime import block_ms
     B, d, h, w, g = PRESETS[name]
     cfg = Cfg(B, d, h, w, g)
     src = ArraySource(images[:B], labels[:B], down_sampling=d, resident=resident)
@@ -47,16 +48,7 @@ def measure(name, resident, images, labels, batches, warmup):
             return ld.next_batch()
         except StopIteration:
             return ld.next_batch()
-    for _ in range(warmup):
-        one()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(batches):
-        one()
-    e1.record()
-    e1.synchronize()
-    ms = e0.elapsed_time(e1) / batches
+    ms = block_ms(one, batches, warm=warmup)
     out_bytes = B * (3 * h * w * 4 + (h // g) * (w // g) * 8)
     src_bytes = B * h * w * 4                                      # the crop's footprint: 3 image bytes + 1 label byte per pixel
     upload = 0 if resident else sum(a.nbytes + b.nbytes for a, b in zip(images[:B], labels[:B]))
