@@ -65,6 +65,7 @@ class HeadsDesc(ctypes.Structure):
 
 
 FS_RENDER_MAX_PANELS = 4
+FS_PNG_BAND_MAX_BYTES = 16384   # filtered bytes of one band of fs_png_deflate (a workgroup's LDS)
 
 
 class RenderDesc(ctypes.Structure):
@@ -129,6 +130,7 @@ SIGNATURES = {
     "fs_train_batch": [c_vp, ctypes.POINTER(TrainBatchDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "fs_resize_u8": [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int],
     "fs_render_prediction": [c_vp, ctypes.POINTER(RenderDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "fs_png_deflate": [c_vp, c_vp, c_int, c_int, c_ll, c_int, c_vp, ctypes.c_size_t, c_vp, c_vp, ctypes.c_size_t],
     "fs_bilinear_bwd": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp, c_vp],
     "fs_bilinear_bwd_nchw": [c_vp, ctypes.POINTER(ResizeDesc), c_vp, c_vp, c_vp],
     "fs_bn_finalize": [c_vp, c_int, c_ll, c_vp, c_vp, c_vp, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -203,6 +205,8 @@ _SPECIAL = {
     "fs_loss_up_workspace_bytes": ([ctypes.POINTER(LogitsDesc)], c_ll),
     "fs_ohem_select_workspace_bytes": ([c_ll], c_ll),
     "fs_train_batch_args_bytes": ([c_int], c_ll),
+    "fs_png_deflate_bound": ([c_int, c_int, c_int], ctypes.c_size_t),
+    "fs_png_deflate_workspace_bytes": ([c_int, c_int, c_int], ctypes.c_size_t),
     "fs_zoom_cell_supported": ([ctypes.POINTER(ZoomDesc)], c_int),
     "fs_workspace_counter_bytes": ([], c_ll),
     "fs_set_deterministic": ([c_int], None),

@@ -913,6 +913,52 @@ def render_prediction(image, maps, palette, composite=None, col=0, image_panel=F
     return span
 
 
+def png_rows_per_band(rows, row_bytes):
+    """Default band height of png_deflate: the largest that still cuts the map into at least 256 bands (one workgroup each: a chip's
+    worth) when it has that many rows, and whose filtered bytes fit a workgroup's LDS (FS_PNG_BAND_MAX_BYTES).  4 at 1024 x 2048."""
+    fit = _lib.FS_PNG_BAND_MAX_BYTES // (int(row_bytes) + 1)
+    if fit < 1:
+        raise ValueError("png_deflate: a row of %d bytes is above the %d filtered bytes of a band" % (row_bytes, _lib.FS_PNG_BAND_MAX_BYTES))
+    return max(1, min((int(rows) - 1) // 255, fit))
+
+
+def png_deflate_sizes(rows, row_bytes, rows_per_band):
+    """(bytes of `out`: fs_png_deflate_bound, bytes of the workspace) of a geometry."""
+    h = _lib.lib()
+    return int(h.fs_png_deflate_bound(rows, row_bytes, rows_per_band)), int(h.fs_png_deflate_workspace_bytes(rows, row_bytes, rows_per_band))
+
+
+def png_deflate(map, rows_per_band=None, out=None, workspace=None, out_bytes=None):
+    """fs_png_deflate: a uint8 device tensor (H, W) or (H, W, 3), unit stride inside a row and any row pitch, -> the zlib stream of its
+    PNG IDAT chunk (Up filter, fixed-Huffman bands of run-length matches: the header states the bytes).  Returns (out, out_bytes): a
+    uint8 buffer of at least the bound and an int64 (1,) device tensor holding the stream's length; both, and the workspace (uint8, 16-byte
+    aligned), are created when not passed.  Two launches on the current stream, nothing is read back."""
+    assert map.dtype == torch.uint8 and map.is_cuda and map.dim() in (2, 3) and map.numel() > 0, "map: a uint8 device tensor (H, W) or (H, W, 3)"
+    H, W = int(map.shape[0]), int(map.shape[1])
+    if map.dim() == 3:
+        assert map.shape[2] == 3 and map.stride(2) == 1 and map.stride(1) == 3, "an (H, W, 3) map has dense rows"
+        row_bytes = 3 * W
+    else:
+        assert map.stride(1) == 1 or W == 1, "an (H, W) map has unit stride inside a row"
+        row_bytes = W
+    pitch = int(map.stride(0)) if H > 1 else row_bytes
+    assert pitch >= row_bytes, "rows overlap"
+    if rows_per_band is None:
+        rows_per_band = png_rows_per_band(H, row_bytes)
+    bound, ws = png_deflate_sizes(H, row_bytes, int(rows_per_band))
+    if out is None:
+        out = torch.empty(bound, dtype=torch.uint8, device=map.device)
+    if workspace is None:
+        workspace = torch.empty(ws, dtype=torch.uint8, device=map.device)
+    if out_bytes is None:
+        out_bytes = torch.empty(1, dtype=torch.int64, device=map.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+    assert out_bytes.dtype == torch.int64 and out_bytes.numel() == 1
+    call("fs_png_deflate", _stream(), _p(map), H, row_bytes, pitch, int(rows_per_band), _p(out), out.numel(), _p(out_bytes), _p(workspace),
+         workspace.numel())
+    return out, out_bytes
+
+
 def deterministic_on():
     """Is the library in its bit-reproducible mode (fs_set_deterministic / FS_DETERMINISTIC=1)?"""
     return bool(_lib.lib().fs_get_deterministic())

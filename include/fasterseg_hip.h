@@ -37,6 +37,8 @@
 #ifndef FASTERSEG_HIP_H
 #define FASTERSEG_HIP_H
 
+#include <stddef.h>   /* size_t (fs_png_deflate) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -856,6 +858,37 @@ typedef struct fs_render_desc {
 } fs_render_desc;
 fs_status fs_render_prediction(void* stream, const fs_render_desc* d, const unsigned char* image, const unsigned char* const maps[4],
                                const unsigned char* palette, const unsigned char* lut, unsigned char* composite, unsigned char* ids);
+/* --- PNG IDAT streams on the device --------------------------------------------------------------------------------- */
+/* Three added symbols: no struct and no existing signature changed, so FS_ABI_VERSION stays 221; a library built before them simply
+ * does not export them.
+ * fs_png_deflate turns a uint8 matrix of rows x row_bytes (row y at src + y * pitch; row_bytes = W for an (H, W) map, 3 W for an
+ * (H, W, 3) picture) into a complete zlib stream for the IDAT chunk of an 8-bit PNG.  The stream is FIXED, byte for byte:
+ *   scanlines  every row is filter type 2 (Up): the byte 2, then row[y] - row[y - 1] mod 256, the row above the first being zeros.
+ *              The filter reads the input, so it crosses band boundaries.
+ *   bands      the rows are cut into bands of rows_per_band rows (the last may be shorter).  A band's filtered bytes, filter bytes
+ *              included, are ONE deflate block BFINAL = 0, BTYPE = 01 (fixed Huffman), followed by an empty stored block: the bits
+ *              000, padding to the byte, 00 00 FF FF.  Every band therefore starts and ends on a byte boundary.
+ *   tokens     a band's filtered bytes are cut into maximal runs of equal bytes (a run never crosses a band boundary).  A run of
+ *              length L emits a literal, floor((L - 1) / 258) matches (length 258, distance 1) and, for r = (L - 1) mod 258, one match
+ *              (length r, distance 1) if r >= 3, else r literals.  Then end of block (symbol 256).
+ *   bit order  RFC 1951: Huffman codes packed from their most significant bit, extra bits from their least significant one.
+ *   stream     78 01, the bands, 01 00 00 FF FF (an empty stored block with BFINAL = 1), the big-endian Adler-32 of all filtered bytes.
+ * A literal costs at most 9 bits and a match never more than the literals it replaces, so with n_b the filtered bytes of band b
+ *   fs_png_deflate_bound = 2 + sum over the bands of (ceil((3 + 9 n_b + 7 + 3) / 8) + 4) + 5 + 4
+ * bytes hold any stream of the geometry; 0 for a geometry that is none (rows < 0, row_bytes <= 0, rows_per_band <= 0).
+ * A band lives in a workgroup's LDS: min(rows, rows_per_band) * (row_bytes + 1) <= FS_PNG_BAND_MAX_BYTES, above: FS_ERR_UNSUPPORTED.
+ * (16384 filtered bytes, their 9/8 bit buffer and the scan scratch are 50 KiB a workgroup of 1024 threads: two of them are a CU's 32
+ * waves, so the LDS does not limit occupancy.)
+ * src: any alignment, pitch >= row_bytes; out: out_capacity >= the bound, nothing behind the stream's last byte is written;
+ * out_bytes: DEVICE pointer, 8-byte aligned, receives the stream's length; workspace: 16-byte aligned, ws_bytes >=
+ * fs_png_deflate_workspace_bytes.  Filtered input, bound and workspace each stay below 2^31 bytes (FS_ERR_UNSUPPORTED).  rows == 0
+ * launches nothing and returns FS_OK.  Two launches (bands, then pack); integers only and no global atomic: equal inputs give equal
+ * bytes.  The PNG file around the stream - signature, IHDR, the IDAT chunk's length and CRC-32, IEND - is the host's to write. */
+#define FS_PNG_BAND_MAX_BYTES 16384
+size_t fs_png_deflate_bound(int rows, int row_bytes, int rows_per_band);
+size_t fs_png_deflate_workspace_bytes(int rows, int row_bytes, int rows_per_band);
+fs_status fs_png_deflate(void* stream, const unsigned char* src, int rows, int row_bytes, long long pitch, int rows_per_band,
+                         unsigned char* out, size_t out_capacity, long long* out_bytes, void* workspace, size_t ws_bytes);
 fs_status fs_exec_program(void* stream, const long long* words, long long n_words, const unsigned char* blob,
                           void* const* slots, int n_slots);
 /* Op word of every command: bits 0-15 the op code, bits 16-39 the stream lane (multi-stream form), bit 40 JOIN (ABI 208): this command
