@@ -111,6 +111,7 @@ extern "C" int fs_sgd_chunk_elems(void) { return SGD_CHUNK; }
 
 extern "C" long long fs_sgd_tensor_chunks(long long numel, int I, int taps, int has_packs) {
     if (numel <= 0 || I <= 0 || taps <= 0) return 0;
+    if (taps > SGD_POS) return 0;             // one input channel's taps must fit a tile row (tile[SGD_TO][SGD_POS + 1]): refused, not walked
     if (!sgd_tiled(taps, has_packs ? (const void*)1 : nullptr, nullptr)) return (numel + SGD_CHUNK - 1) / SGD_CHUNK;
     const long long O = numel / ((long long)taps * I);
     const int IT = sgd_tile_i(taps);

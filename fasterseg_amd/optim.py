@@ -18,6 +18,7 @@ from . import kernels as K
 
 _TENSOR = np.dtype([("p", "<u8"), ("g_off", "<i8"), ("numel", "<i8"), ("I", "<i4"), ("taps", "<i4"), ("pack_fwd", "<u8"),
                     ("pack_flip", "<u8")])     # fs_sgd_tensor
+MAX_TAPS = 256                                 # csrc/optim.hip SGD_POS: the largest R * S the tiled walk holds
 
 
 class FlatSGD:
@@ -38,6 +39,12 @@ class FlatSGD:
         self.unused = unused
         self._ever_touched = None
         params = sync.params
+        for p in params:
+            # the tiled walk stages all taps of one input channel in one LDS row of MAX_TAPS positions; the launch cannot check the
+            # device table, so a larger filter is refused here (fs_sgd_tensor_chunks returns 0 for it)
+            if p.dim() == 4 and p.shape[2] * p.shape[3] > MAX_TAPS:
+                raise ValueError("FlatSGD: a filter of shape %s has %d taps, the update kernel walks at most %d"
+                                 % (tuple(p.shape), p.shape[2] * p.shape[3], MAX_TAPS))
         dev = sync.flat.device
         if dev.type != "cuda":
             raise RuntimeError("FlatSGD runs on the HIP kernels only (no CPU path)")

@@ -443,7 +443,10 @@ fs_status fs_weighted_sum_dots(void* stream, long long pixels, int C, int n, con
  * skips tensor t (a parameter that received no gradient is left alone, as torch does for grad=None).  grad_scale: device
  * scalar multiplied into every gradient (the clip factor), may be null.
  * Resident packs: the same pass rewrites the packed filter copies the conv kernels read (fs_conv_desc.w_os/w_ts), so no
- * per-forward fs_pack_weight launches are needed; pack_only=1 just (re)builds them from the current parameters. */
+ * per-forward fs_pack_weight launches are needed; pack_only=1 just (re)builds them from the current parameters.
+ * Limit: taps <= 256 (a 16 x 16 filter).  The tiled walk stages all taps of an input channel in one 256-position LDS row; the launch
+ * cannot inspect the device table, so the caller must not describe a larger filter: fs_sgd_tensor_chunks returns 0 for it (no
+ * blocks), and optim.FlatSGD raises ValueError. */
 typedef struct fs_sgd_tensor {
     float* p;
     long long g_off;
