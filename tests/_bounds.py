@@ -1,7 +1,8 @@
 """Per-element error bounds of the kernels against fp64 references: the 16-bit inference kernels (tests/test_f16_kernels_gpu.py,
 tests/test_bf16_kernels_gpu.py, tests/test_bounds_selfcheck.py) and, in the second half of the module, the training backward kernels
-(tests/test_bwd_bounds_gpu.py, tests/test_bwd_bounds_selfcheck.py, the weight gradients of tests/_grouped_cases.py).  Every helper takes
-the storage dtype; `For(dtype)` binds it, so a test module names its type once.
+(tests/test_bwd_bounds_gpu.py, tests/test_bwd_bounds_selfcheck.py, the weight gradients of tests/_grouped_cases.py), and in the third
+section the train-mode BatchNorm forward (tests/test_bn_fwd_bounds_gpu.py, tests/test_bn_fwd_bounds_selfcheck.py, the BatchNorm units of
+tests/_grouped_cases.py).  Every helper takes the storage dtype; `For(dtype)` binds it, so a test module names its type once.
 
 UNIT[dtype] is the unit roundoff of one round-to-nearest store: half an ulp relative to the value, 2^-p for a p-bit significand (hidden
 bit included).  fp16 has 11 bits, bf16 has 8: 2^-8, not 2^-9 - a correctly rounded bf16 value just above a power of two is off by up to
@@ -372,3 +373,150 @@ def old_bars(err, ref):
     """how many elements the three older bars flag: 2e-2 max|ref|, 2e-4 max|ref| + 1e-4, 1e-4 + 1e-4 |ref|"""
     m = float(ref.abs().max())
     return int((err > 2e-2 * m).sum()), int((err > 2e-4 * m + 1e-4).sum()), int((err > 1e-4 + 1e-4 * ref.abs()).sum())
+
+
+# =========================================================================================================================================
+# The train-mode BatchNorm forward.  An any-order fp32 sum of n terms has to be allowed n roundings, and at a few thousand pixels that
+# allowance hides a lost pixel.  The sharp instrument is the "grid" family of operands: z = j / 16 with small integers j, whose sums
+# and sums of squares are exact in fp32 in ANY order (atomics, wave shuffles, block partials, s2 += v * v contracted into an fma or
+# not), so the bound has no term in n.  Every grid value is a bf16 number.  The "normal" family is the older tests' 1.5 N(0, 1) + 0.3.
+# =========================================================================================================================================
+BN_EPS, BN_MOMENTUM = 1e-5, 0.1
+BN_GRID_DEN, BN_GRID_JMAX = 16, 64
+BN_NORMAL_N_MAX = 2048                  # n^2 2^-23 <= 1/2, the reasoning of WGRAD_P_MAX: one lost pixel stands out of n roundings
+
+
+def f32(v):
+    """the fp32 number nearest to a Python float, as a Python float (eps and momentum reach the kernels as fp32 arguments)"""
+    return float(np.float32(v))
+
+
+def bn_fwd_operands(dtype, G, n, C, seed, family, jmax=BN_GRID_JMAX):
+    """(z (G, n, C), gamma, beta, rm0, rv0 (C)) in fp64; z values of `dtype`, the parameters fp32 numbers.  One gamma is negative.
+    family="grid": z = j / 16, j uniform in [-jmax / 4, jmax]: a non-zero mean, so E[z^2] - m^2 cancels about half its bits.  Channel 0
+    is constant (j = 3 jmax / 4: its variance is exactly 0, var clamps and invstd = 1 / sqrt(eps)), channel 1 has a small variance on
+    a large mean (j in {jmax - 1, jmax}).  sum_n j^2 < 2^24 and n max|j| < 2^24 per (group, channel) are asserted: every partial sum
+    of z and of z^2 is then an integer multiple of 2^-8 below 2^16, exact in fp32.  A caller with more pixels than jmax = 64 allows
+    narrows jmax; the assertion stays.
+    family="normal": 1.5 N(0, 1) + 0.3 rounded to `dtype`, at most BN_NORMAL_N_MAX pixels per group."""
+    g = torch.Generator().manual_seed(seed)
+    if family == "grid":
+        assert jmax % 4 == 0 and 4 <= jmax <= BN_GRID_JMAX
+        j = torch.randint(-jmax // 4, jmax + 1, (G, n, C), generator=g).double()
+        j[:, :, 0] = 3 * jmax // 4
+        if C > 1:
+            j[:, :, 1] = torch.randint(jmax - 1, jmax + 1, (G, n), generator=g).double()
+        assert float((j * j).sum(1).max()) < 2.0 ** 24, "sum j^2 = %d: the sums of squares would round" % int((j * j).sum(1).max())
+        assert n * float(j.abs().max()) < 2.0 ** 24
+        z = j / BN_GRID_DEN
+        assert bool((z.to(torch.bfloat16).double() == z).all())
+    else:
+        assert family == "normal", family
+        assert n <= BN_NORMAL_N_MAX, "n = %d: a lost pixel would hide in a bound of n roundings" % n
+        z = torch.randn(G, n, C, generator=g).to(dtype).double().mul(1.5).add(0.3).to(dtype).double()
+    gamma = (torch.randn(C, generator=g).abs() + 0.5).float().double()
+    gamma[C // 2] = -gamma[C // 2]
+    beta = (torch.randn(C, generator=g) * 0.2).float().double()
+    rm0 = (torch.randn(C, generator=g) * 0.1).float().double()
+    rv0 = (torch.randn(C, generator=g).abs() + 0.5).float().double()
+    return z, gamma, beta, rm0, rv0
+
+
+def bn_fwd(dtype, z, gamma, beta, rm0, rv0, relu_from, exact_sums, eps=BN_EPS, momentum=BN_MOMENTUM):
+    """Train-mode BatchNorm (+ReLU from channel `relu_from` on; None: no ReLU, 0: every channel) of z (G, n, C), G groups normalised
+    independently with the same parameters, running statistics updated group after group.  References in fp64 and per-element bounds:
+      s1 = sum z, s2 = sum z^2 in any order: e1 = n 2^-23 sum|z|, e2 = (n + 1) 2^-23 sum z^2 (the product too); both 0 with exact_sums
+      m = s1 / n:    em = e1 / n + 2^-23 |m|;      q = s2 / n:    eq = e2 / n + 2^-23 q
+      var = max(q - m^2, 0):   ev = eq + 2 |m| em + em^2 + 2 2^-23 (q + m^2)        (product and subtraction, fused or not)
+      invstd = 1 / sqrt(var + eps) as an INTERVAL: [(1 - 3 2^-23) / sqrt(var + ev + eps), (1 + 3 2^-23) / sqrt(max(var - ev, 0) + eps)]
+        (add, sqrt, divide).  No first-order form: at a constant channel ev is of the size of eps.  e_is = the wider side.
+      scale = gamma invstd:   e_sc = |gamma| e_is + 2^-23 (|scale| + |gamma| e_is)
+      shift = beta - m scale: e_sh = |m| e_sc + |scale| em + em e_sc + 2 2^-23 (|beta| + |m scale| + |m| e_sc + |scale| em)
+      y = z scale + shift:    e_y = |z| e_sc + e_sh + 2 2^-23 (|z scale| + |shift| + |z| e_sc + e_sh), or the form below that takes
+        the scale's error once, whichever is smaller; ReLU is 1-Lipschitz; one store.
+      running statistics r <- (1 - momentum) r + momentum v per group in order, as `_stage` propagates: four roundings (1 - momentum,
+        two products, the sum) on the terms and on the errors carried in; v = m, or var n / (n - 1) with two more roundings.
+    Returns mean / invstd / scale / shift (G, C) with *_bound (invstd also invstd_lo, invstd_hi), saved / saved_bound (G, 4, C),
+    y / y_bound (G, n, C), rm / rv with *_bound (C), stats = [s1 | s2] (G, 2 C)."""
+    G, n, C = z.shape
+    eps, momentum = f32(eps), f32(momentum)
+    s1, s2 = z.sum(1), (z * z).sum(1)
+    e1, e2 = (0.0, 0.0) if exact_sums else (n * E32 * z.abs().sum(1), (n + 1) * E32 * s2)
+    m, q = s1 / n, s2 / n
+    em, eq = e1 / n + E32 * m.abs(), e2 / n + E32 * q
+    var = (q - m * m).clamp(min=0.0)
+    ev = eq + 2 * m.abs() * em + em * em + 2 * E32 * (q + m * m)
+    is_ = 1.0 / torch.sqrt(var + eps)
+    lo, hi = (1 - 3 * E32) / torch.sqrt(var + ev + eps), (1 + 3 * E32) / torch.sqrt((var - ev).clamp(min=0.0) + eps)
+    e_is = torch.maximum(hi - is_, is_ - lo)
+    ga, be = gamma.view(1, C), beta.view(1, C)
+    scale = ga * is_
+    e_sc = ga.abs() * e_is + E32 * (scale.abs() + ga.abs() * e_is)
+    shift = be - m * scale
+    e_sh = m.abs() * e_sc + scale.abs() * em + em * e_sc + 2 * E32 * (be.abs() + (m * scale).abs() + m.abs() * e_sc + scale.abs() * em)
+    sc, sh, esc, esh = scale[:, None], shift[:, None], e_sc[:, None], e_sh[:, None]
+    y = z * sc + sh
+    e_y = z.abs() * esc + esh + 2 * E32 * ((z * sc).abs() + sh.abs() + z.abs() * esc + esh)
+    # the same y, with the scale's error taken ONCE: every body multiplies z and (inside shift) m by one and the same computed invstd, so
+    # y^ - y = (z - m)(s^ - s) + (m - m^) s^ + roundings.  Three roundings on shift's terms (m * gamma * invstd is two products where
+    # scale is one, and the subtraction), two on y's.  Both forms hold; the smaller is the bound.  This one keeps e_is out of a channel
+    # whose values lie close to its mean - the constant channel above all, where y = beta whatever invstd is.
+    mm, emm = m[:, None], em[:, None]
+    s_hi = sc.abs() + esc
+    e_yc = (z - mm).abs() * esc + emm * s_hi + 3 * E32 * (be.abs() + (mm.abs() + emm) * s_hi) + 2 * E32 * (z.abs() * s_hi + sh.abs() + esh)
+    e_y = torch.minimum(e_y, e_yc)
+    if relu_from is not None:
+        y = torch.cat([y[..., :relu_from], F.relu(y[..., relu_from:])], -1)
+    out = dict(mean=m, mean_bound=em, invstd=is_, invstd_bound=e_is, invstd_lo=lo, invstd_hi=hi, scale=scale, scale_bound=e_sc, shift=shift,
+               shift_bound=e_sh, y=y, y_bound=e_y + UNIT[dtype] * (y.abs() + e_y) + TINY, stats=torch.cat([s1, s2], 1))
+    out["saved"], out["saved_bound"] = torch.stack([m, is_, scale, shift], 1), torch.stack([em, e_is, e_sc, e_sh], 1)
+    unb = n / (n - 1.0) if n > 1 else 1.0
+    vu, evu = var * unb, (ev + (2 * E32 * (var + ev) if n > 1 else 0.0)) * unb
+    keep = 1.0 - momentum
+    for name, r, v, e_v in (("rm", rm0.clone(), m, em), ("rv", rv0.clone(), vu, evu)):
+        er = torch.zeros_like(r)
+        for g in range(G):
+            er = keep * er + momentum * e_v[g] + 4 * E32 * (keep * (r.abs() + er) + momentum * (v[g].abs() + e_v[g]))
+            r = keep * r + momentum * v[g]
+        out[name], out[name + "_bound"] = r, er
+    return out
+
+
+def assert_between(got, lo, hi, what):
+    got = got.detach().double().cpu()
+    bad = ~((got >= lo) & (got <= hi))                                          # a NaN is outside
+    print("%s: worst position in [lo, hi] %.3f" % (what, float(((got - lo) / (hi - lo)).max())))
+    assert not bool(bad.any()), "%s: %d of %d outside the interval" % (what, int(bad.sum()), got.numel())
+
+
+BN_FWD_OUTPUTS = ("mean", "invstd", "scale", "shift", "y", "rm", "rv")
+
+
+def bn_fwd_check(want, got, what, only=BN_FWD_OUTPUTS):
+    """got: dict with any of saved (G, 4, C), y (G, n, C), rm, rv (C), every one finite and within its bound at every element; the inverse
+    deviation within its interval too"""
+    got = {k: v.detach().double().cpu() for k, v in got.items()}
+    if "saved" in got:
+        sv = got.pop("saved").reshape(want["saved"].shape)
+        got.update(mean=sv[:, 0], invstd=sv[:, 1], scale=sv[:, 2], shift=sv[:, 3])
+    for k in only:
+        if k in got:
+            v = got[k].reshape(want[k].shape)
+            assert bool(torch.isfinite(v).all()), "%s %s: %d elements are not finite (never written?)" % (what, k, int((~torch.isfinite(v)).sum()))
+            assert_within(v, want[k], want[k + "_bound"], "%s %s" % (what, k))
+            if k == "invstd":
+                assert_between(v, want["invstd_lo"], want["invstd_hi"], "%s invstd interval" % what)
+
+
+def bn_old_bars(dtype, got, want):
+    """which outputs the bars of tests/test_bn_group_gpu.py flag (its `_close`: y at 2e-5 + 2e-5 max|ref| in fp32 and 2e-2 max|ref| in bf16;
+    mean, invstd and the running statistics at the fp32 bar): the names, in BN_FWD_OUTPUTS order"""
+    flagged = []
+    for k in ("mean", "invstd", "y", "rm", "rv"):
+        ref = want[k]
+        err = float((got[k].double().reshape(ref.shape) - ref).abs().max())
+        top = float(ref.abs().max())
+        tol = 2e-2 * max(top, 1e-3) if (k == "y" and dtype != torch.float32) else 2e-5 + 2e-5 * top
+        if not err <= tol:
+            flagged.append(k)
+    return flagged

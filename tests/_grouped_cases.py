@@ -508,15 +508,31 @@ BN_TABLE = [
 EPS, MOMENTUM = 1e-5, 0.1
 
 
+BN_FAMILIES = ["normal", "grid"]
+
+
 class BnProblem:
-    def __init__(self, spec, seed):
+    """family "normal": 1.5 N(0, 1) + 0.3, held to the bars of tests/test_bn_group_gpu.py.  family "grid" (tests/_bounds.bn_fwd_operands:
+    z = j / 16 with exactly summable values, a constant channel, a channel with a small variance on a large mean, a negative gamma):
+    the forward is held to the per-element exact-sum bound of tests/_bounds.bn_fwd instead - y, the four blocks of `saved` and the
+    running statistics.  The per-tensor bars were set on the normal family; an honest kernel's cancellation in E[z^2] - m^2 of the
+    grid's small-variance channel lies beyond them and inside the bound (tests/test_bn_fwd_bounds_selfcheck.py)."""
+
+    def __init__(self, spec, seed, family="normal"):
         self.ppg, self.G, self.C, self.relu, self.dtype, self.acc = spec
         G, ppg, C, dtype = self.G, self.ppg, self.C, self.dtype
-        self.pixels = G * ppg
-        self.z0 = q(rnd(self.pixels, C, seed=seed) * 1.5 + 0.3, dtype)
+        self.pixels, self.family, self.bound = G * ppg, family, None
         self.dy0 = q(rnd(self.pixels, C, seed=seed + 1), dtype)
-        gamma, beta = rnd(C, seed=seed + 2).abs().float().double() + 0.5, (rnd(C, seed=seed + 3) * 0.2).float().double()
-        self.rm0, self.rv0 = (rnd(C, seed=seed + 4) * 0.1).float().double(), rnd(C, seed=seed + 5).abs().float().double() + 0.5
+        if family == "grid":
+            from tests import _bounds as B
+            z, gamma, beta, self.rm0, self.rv0 = B.bn_fwd_operands(dtype, G, ppg, C, seed, "grid")
+            self.z0 = z.reshape(self.pixels, C)
+            self.bound = B.bn_fwd(dtype, z, gamma, beta, self.rm0, self.rv0, 0 if self.relu else None, True, eps=EPS, momentum=MOMENTUM)
+        else:
+            assert family == "normal", family
+            self.z0 = q(rnd(self.pixels, C, seed=seed) * 1.5 + 0.3, dtype)
+            gamma, beta = rnd(C, seed=seed + 2).abs().float().double() + 0.5, (rnd(C, seed=seed + 3) * 0.2).float().double()
+            self.rm0, self.rv0 = (rnd(C, seed=seed + 4) * 0.1).float().double(), rnd(C, seed=seed + 5).abs().float().double() + 0.5
         self.dg0, self.db0 = rnd(C, seed=seed + 6).float().double(), rnd(C, seed=seed + 7).float().double()
         self.gamma, self.beta = dev(gamma, F32), dev(beta, F32)
         # reference, group after group (what the reference does when it evaluates one module on several inputs in turn)
@@ -583,13 +599,18 @@ class BnProblem:
         w, dtype = self.want, self.dtype
         y = self.y.read()
         assert bool(torch.isfinite(y).all()), what + ": y holds unwritten elements"
-        close(y, w["y"], dtype, what + " y")
         saved = self.saved.read().view(self.G, 4, self.C)
-        assert bool(torch.isfinite(saved[:, :2]).all()), what + ": saved statistics hold unwritten elements"
-        close(saved[:, 0], w["mean"], F32, what + " saved mean", scale=s["mean"])
-        close(saved[:, 1], w["invstd"], F32, what + " saved invstd", scale=s["invstd"])
-        close(self.rm.read(), w["rm"], F32, what + " running_mean after %d sequential updates" % self.G, scale=s["rm"])
-        close(self.rv.read(), w["rv"], F32, what + " running_var", scale=s["rv"])
+        if self.family == "grid":
+            from tests import _bounds as B
+            assert bool(torch.isfinite(saved).all()), what + ": saved holds unwritten elements"
+            B.bn_fwd_check(self.bound, dict(saved=saved, y=y.view(self.G, self.ppg, self.C), rm=self.rm.read(), rv=self.rv.read()), what + " (grid)")
+        else:
+            close(y, w["y"], dtype, what + " y")
+            assert bool(torch.isfinite(saved[:, :2]).all()), what + ": saved statistics hold unwritten elements"
+            close(saved[:, 0], w["mean"], F32, what + " saved mean", scale=s["mean"])
+            close(saved[:, 1], w["invstd"], F32, what + " saved invstd", scale=s["invstd"])
+            close(self.rm.read(), w["rm"], F32, what + " running_mean after %d sequential updates" % self.G, scale=s["rm"])
+            close(self.rv.read(), w["rv"], F32, what + " running_var", scale=s["rv"])
         assert int(self.nbt.view[0]) == 5 + self.G, what + ": num_batches_tracked"
         for t in (self.y, self.z, self.saved, self.rm, self.rv, self.nbt, self.stats):
             t.assert_surroundings(what)
@@ -615,8 +636,9 @@ class BnProblem:
         return float((dz - w["dz"]).abs().max())
 
 
-def bn_problems(n):
-    all_ = cached("bn", None, lambda: [BnProblem(s, 900 + 10 * i) for i, s in enumerate(BN_TABLE)])
+def bn_problems(n, family="normal"):
+    """the first n problems of the table in one operand family (operands and references built once per family, outputs fresh)"""
+    all_ = cached("bn", family, lambda: [BnProblem(s, 900 + 10 * i, family) for i, s in enumerate(BN_TABLE)])
     ps = all_[:n]
     for p in ps:
         p.reset()
@@ -1087,14 +1109,16 @@ def child_bn():
     from fasterseg_amd.program import OP_BN_UNIT_BWD, OP_BN_UNIT_FWD
     mixed = os.environ.get("FS_GROUP_BN_MIXED", "1")[:1] != "0"
     for n in SIZES:
-        ps = bn_problems(n)
-        for backward, op in ((False, OP_BN_UNIT_FWD), (True, OP_BN_UNIT_BWD)):
-            kernels = recorded(lambda: run_programs(op, [[p.bwd_args() if backward else p.fwd_args()] for p in ps]))
-            assert only(kernels, BN_KERNELS) == bn_expected(ps, backward, mixed), (kernels, bn_expected(ps, backward, mixed))
-            for i, p in enumerate(ps):
-                what = "bn %s n=%d #%d %s" % ("bwd" if backward else "fwd", n, i, BN_TABLE[i][:5])
-                err = p.verify_bwd(what) if backward else p.verify_fwd(what)
-                print("%s max err %.3e" % (what, err), flush=True)
+        for family in BN_FAMILIES:
+            ps = bn_problems(n, family)
+            # the backward's bars were set on the normal family, whose forward it follows
+            for backward, op in ((False, OP_BN_UNIT_FWD), (True, OP_BN_UNIT_BWD))[:2 if family == "normal" else 1]:
+                kernels = recorded(lambda: run_programs(op, [[p.bwd_args() if backward else p.fwd_args()] for p in ps]))
+                assert only(kernels, BN_KERNELS) == bn_expected(ps, backward, mixed), (kernels, bn_expected(ps, backward, mixed))
+                for i, p in enumerate(ps):
+                    what = "bn %s %s n=%d #%d %s" % ("bwd" if backward else "fwd", family, n, i, BN_TABLE[i][:5])
+                    err = p.verify_bwd(what) if backward else p.verify_fwd(what)
+                    print("%s max err %.3e" % (what, err), flush=True)
 
 
 if __name__ == "__main__":

@@ -120,7 +120,9 @@ def test_weight_gradients_in_bit_reproducible_mode(route):
 def test_grouped_batchnorm_units(n):
     """OP_BN_UNIT_FWD / _BWD over k programs: column kernels (96 .. 512 pixels per group; 4 groups through the generic kernel), grid-wide
     passes (513, 3072), 1 / 2 / 4 batch groups, ReLU on / off, fp32 and bf16 problems in ONE call, with and without dgamma / dbeta
-    accumulators; running statistics after the groups' sequential updates."""
+    accumulators; running statistics after the groups' sequential updates.  The forward runs twice: on exactly summable operands, held per
+    element to tests/_bounds.bn_fwd (y, the four blocks of `saved`, the running statistics), and on the normal operands at the older bars,
+    whose y and `saved` the backward then reads."""
     ps = G.bn_problems(n)
     op = P()
     if n == 13:          # the expectation itself: the full table must reach every grouped BatchNorm kernel of the default routing
@@ -128,6 +130,11 @@ def test_grouped_batchnorm_units(n):
                                             "chan_reduce_kernel": 1, "bn_train_apply_kernel": 1}
         assert G.bn_expected(ps, True) == {"bn_group_bwd_group_kernel": 2, "bn_bwd_mixed_group_kernel": 2, "bn_bwd_apply_group_kernel": 2,
                                            "chan_reduce_kernel": 1, "bn_bwd_apply_kernel": 1}
+    grid = G.bn_problems(n, "grid")          # the same table on exactly summable operands: the forward per element (tests/_bounds.bn_fwd)
+    kernels = G.recorded(lambda: G.run_programs(op.OP_BN_UNIT_FWD, [[p.fwd_args()] for p in grid]))
+    assert G.only(kernels, G.BN_KERNELS) == G.bn_expected(grid, False), kernels
+    for i, p in enumerate(grid):
+        p.verify_fwd("bn fwd problem %d of %d %s" % (i, n, G.BN_TABLE[i]))
     kernels = G.recorded(lambda: G.run_programs(op.OP_BN_UNIT_FWD, [[p.fwd_args()] for p in ps]))
     assert G.only(kernels, G.BN_KERNELS) == G.bn_expected(ps, False), kernels
     for i, p in enumerate(ps):
